@@ -20,9 +20,19 @@ runs independent batches of 64 (frame-parallel, weak scaling, no data-path colle
 sync on both sides of exactly K steps, max over ranks; value = all ranks' images / that time.
 ``--dry-run`` runs the same control flow on CPU with gloo (no device work; tests/test_bench_dist.py).
 
-Rank 0 prints ONE JSON line, the last line of stdout, kept to a few KB (``compact_record``: contract fields, roofline,
-cpu_baseline, pose errors, one summary per sub-record); the full record with the per-kernel tables and every sub-record
-goes to ``--detail-out`` (default gpurun_out/bench_detail.json). Fields: DESIGN.md section 9.
+A plain run (``bench.py --gpus 1 --steps K --warmup W``) does only what the headline figure needs: set-up, the settle
+phase and W warm-up steps, the K timed steps (with the shader-clock stamps just outside them), ``--dump-outputs`` if
+given, and the result line. ``--dump-outputs DIR`` writes what the last timed step returned to its caller (the decode
+dict of ``StreamPipeline.submit``: quaternion, position, soft orientation histogram, raw head outputs, status) as
+``DIR/<name>.npy`` in float32; weights and frames are seeded, so the same arguments give the same inputs in every run.
+
+``--full`` adds everything else, all outside the timed steps: the on-box peak microbenchmark (before the warm-up), the
+single-stream HIP-event leg (roofline, per-kernel table), the CPU baseline and the pose errors against the FP32 oracle,
+the int8 / fp16x2 / fp16 sub-records, the sharp-head check, keypoint mode and EPnP, and the ``--detail-out`` sidecar.
+
+Rank 0 prints ONE JSON line, the last line of stdout, kept to a few KB (``compact_record``: contract fields and, with
+``--full``, roofline, cpu_baseline, pose errors, one summary per sub-record); ``--full`` also writes the full record
+with the per-kernel tables and every sub-record to the ``--detail-out`` file. Fields: DESIGN.md section 9.
 """
 from __future__ import annotations
 
@@ -236,6 +246,20 @@ def time_steps(step, n_warm, n_steps, sync, barrier, probe=None, settle_s=0.0, k
     if probe is not None:
         probe.stop()
     return el, out
+
+
+def dump_outputs(out: dict, path: str) -> None:
+    """--dump-outputs: every array of the last timed step's decode dict (what a caller of StreamPipeline.submit
+    receives) as ``path/<name>.npy``, float32 (the int32 status words included). The URSONet outputs of one batch are
+    under 1 MB, far below the 64 MB a dump may take; a larger output is refused rather than sampled."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in out.items() if isinstance(v, torch.Tensor)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f'--dump-outputs: {total} bytes'
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), a)
 
 
 def roofline(prof, steps, B, traffic_path, peaks=None, int8=False):
@@ -562,6 +586,13 @@ def main():
                     help='replay each (stream, input batch) forward + decode as a recorded HIP graph (StreamPipeline.use_graphs)')
     ap.add_argument('--frame-buffers', type=int, default=6,
                     help='distinct device batches the timed steps rotate over (6 x 50 MB > 256 MB Infinity Cache)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline figure: measured peaks, the roofline / per-kernel leg, the CPU baseline, '
+                         'pose errors, the int8 / fp16x2 / fp16 sub-records, the sharp-head check, keypoint mode and '
+                         'the --detail-out sidecar (the --no-... switches below drop single parts of it)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy '
+                         '(float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-int8', action='store_true', help='skip the C5 (int8) sub-record')
     ap.add_argument('--no-keypoint', action='store_true', help='skip the keypoint-mode / EPnP sub-record')
@@ -659,18 +690,20 @@ def main():
     peaks = None
     probe = None
     if not args.dry_run:
-        if rank == 0 and not args.no_peaks:
+        if rank == 0 and args.full and not args.no_peaks:
             peaks = measure_peaks(local)                   # < 1 s, before the warm-up
         probe = ClockProbe(dev)
         barrier()
     statuses = []
     elapsed, out = time_steps(step, args.warmup, args.steps, sync, barrier, probe,
                               0.0 if args.dry_run else args.settle, keep=lambda o: statuses.append(o['status']))
+    if args.dump_outputs and rank == 0:   # before any later leg runs on the pipeline's engines and buffers again
+        dump_outputs(out, args.dump_outputs)
     elapsed = max_over_ranks(elapsed, dev)
     assert len(statuses) == args.steps and not torch.stack(statuses).any().item(), 'decode reported NaN in a timed step'
 
     leg_probe = None
-    if not args.dry_run:
+    if args.full and not args.dry_run:
         # roofline leg: per-kernel HIP events on the engine's stream, K more steps on one stream, with the shader
         # clock of the leg stamped around it (the roofline's achieved rate is priced at this clock)
         leg_probe = ClockProbe(dev)
@@ -722,7 +755,7 @@ def main():
             rec['sclk_timed_region'] = probe.mhz()
         if args.dry_run:
             rec['dry_run'] = True
-        else:
+        elif args.full:
             rec['roofline'] = roofline(prof, args.steps, B, args.traffic, peaks, int8=args.dtype == 'int8')
             leg_clk = leg_probe.mhz()
             rec['roofline']['sclk_mhz'] = leg_clk['sclk_mhz'] if leg_clk else None
@@ -750,8 +783,9 @@ def main():
                                                     rec['pose_err_vs_fp32']['within_tolerance'])
             if world == 1 and not args.no_keypoint:
                 rec['keypoint_mode'] = run_keypoint(args, dev, with_ref=not args.no_cpu_baseline)
-        # full record (per-kernel tables, every sub-record) to the sidecar; the LAST stdout line is the compact headline
-        detail = args.detail_out or None
+        # --full: full record (per-kernel tables, every sub-record) to the sidecar; the LAST stdout line is the compact
+        # headline
+        detail = (args.detail_out or None) if args.full else None
         if detail:
             try:
                 os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)

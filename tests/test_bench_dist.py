@@ -9,6 +9,8 @@ import socket
 import subprocess
 import sys
 
+import pytest
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -30,7 +32,7 @@ def test_bench_two_rank_dry_run(tmp_path):
     detail = tmp_path / 'detail.json'
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
            '127.0.0.1', '--master-port', str(_free_port()), os.path.join(REPO, 'bench.py'), '--gpus', '2',
-           '--steps', '3', '--warmup', '1', '--dry-run', '--detail-out', str(detail)]
+           '--steps', '3', '--warmup', '1', '--dry-run', '--full', '--detail-out', str(detail)]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -42,6 +44,54 @@ def test_bench_two_rank_dry_run(tmp_path):
     assert rec['dry_run'] is True and rec['n_gpus'] == 2 and rec['steps'] == 3 and rec['warmup'] == 1
     assert rec['config']['global_batch'] == 128 and rec['scaling'] == 'weak'
     assert rec['value'] > 0 and rec['unit'] == 'images/sec'
+
+
+def _run_bench(*args):
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', *args], cwd=REPO,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads(r.stdout.rstrip().splitlines()[-1])
+
+
+def test_plain_dry_run_is_lean_and_dumps(tmp_path):
+    """Without --full: the contract fields only (no sidecar, no sub-record), --steps is the number of timed steps, and
+    --dump-outputs writes the last step's arrays as float32 .npy files."""
+    import numpy as np
+    detail, dump = tmp_path / 'detail.json', tmp_path / 'dump'
+    rec = _run_bench('--steps', '4', '--warmup', '2', '--dry-run', '--detail-out', str(detail), '--dump-outputs',
+                     str(dump))
+    assert rec['steps'] == 4 and rec['warmup'] == 2 and rec['ms_per_step'] >= 0 and rec['unit'] == 'images/sec'
+    assert rec['higher_is_better'] is True and rec['dtype'] == 'fp16mx'
+    assert not detail.exists() and 'detail' not in rec and 'cpu_baseline' not in rec and 'sub_records' not in rec
+    assert [p.name for p in dump.iterdir()] == ['status.npy']
+    st = np.load(dump / 'status.npy')
+    assert st.dtype == np.float32 and not st.any()
+
+
+@pytest.mark.gpu
+def test_plain_gpu_run_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run on the GPU (tiny workload): only the headline fields, and --dump-outputs holds the decode dict of
+    the last timed step -- float32, finite, unit quaternions, a normalised soft histogram, status zero -- the same
+    from run to run (seeded weights and frames)."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        rec = _run_bench('--steps', '3', '--warmup', '1', '--settle', '0', '--batch', '2', '--size', '64',
+                         '--dump-outputs', str(tmp_path / f'd{k}'))
+        assert rec['steps'] == 3 and rec['ms_per_step'] > 0 and rec['value'] > 0
+        assert abs(rec['value'] - 2 / (rec['ms_per_step'] * 1e-3)) <= 0.01 * rec['value']
+        for moved in ('roofline', 'peak_measured', 'cpu_baseline', 'pose_err_vs_fp32', 'sub_records', 'detail'):
+            assert moved not in rec, moved
+        dumps.append({p.name[:-4]: np.load(p) for p in sorted((tmp_path / f'd{k}').iterdir())})
+    a, b = dumps
+    assert set(a) == {'ori', 'pos', 'ori_soft', 'raw0', 'raw1', 'status'}
+    assert a['ori'].shape == (2, 4) and a['pos'].shape == (2, 3) and a['raw0'].shape == a['ori_soft'].shape == (2, 1728)
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), k
+        np.testing.assert_allclose(v, b[k], rtol=0, atol=1e-5, err_msg=k)   # fp32 atomics: summation order
+    assert not a['status'].any()
+    np.testing.assert_allclose(np.linalg.norm(a['ori'], axis=1), 1.0, atol=1e-5)
+    np.testing.assert_allclose(a['ori_soft'].sum(axis=1), 1.0, atol=1e-5)
 
 
 def test_headline_line_compact_on_a_full_gpu_record():

@@ -10,6 +10,6 @@ timeout -k 10 700 python -u -m pytest $R/tests -m gpu -x -q --timeout 120 --time
 tail -2 $R/gpurun_out/pt.log
 timeout -k 10 400 python -u $R/tools/ab.py $R/${BASE:-abbase/base.so} $N > $R/gpurun_out/ab.log 2>&1 || { tail -20 $R/gpurun_out/ab.log; exit 1; }
 head -30 $R/gpurun_out/ab.log
-timeout -k 10 300 python $R/bench.py --no-cpu-baseline > $R/gpurun_out/bq.json 2> $R/gpurun_out/bq.err || { tail -20 $R/gpurun_out/bq.err; exit 1; }
-python -c "
-import json; d=json.load(open('$R/gpurun_out/bq.json')); print('value', d['value'], 'ms', d['ms_per_step'], 'sclk', d.get('sclk_timed_region',{}).get('sclk_mhz'), 'err', d.get('pose_err_vs_fp32'))"
+BQ=$(timeout -k 10 300 python $R/bench.py --full --no-cpu-baseline) || exit 1
+BQ="$BQ" python -c "
+import json, os; d=json.loads(os.environ['BQ'].splitlines()[-1]); print('value', d['value'], 'ms', d['ms_per_step'], 'sclk', d.get('sclk_timed_region',{}).get('sclk_mhz'), 'err', d.get('pose_err_vs_fp32'))"

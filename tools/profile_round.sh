@@ -14,10 +14,10 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p $O
-timeout -k 10 300 python3 $R/bench.py > $O/bench_$TAG.json 2> $O/bench_$TAG.err
+timeout -k 10 300 python3 $R/bench.py --full > $O/bench_$TAG.json 2> $O/bench_$TAG.err
 echo "bench ok"
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -o run --output-format csv \
-  -- python3 $R/bench.py --steps 10 --no-cpu-baseline --no-int8 --no-keypoint --no-x2 --sharp-frames 0 --no-peaks) \
+  -- python3 $R/bench.py --full --steps 10 --no-cpu-baseline --no-int8 --no-keypoint --no-x2 --sharp-frames 0 --no-peaks) \
   > $O/prof_$TAG.log 2>&1
 echo "stats ok"
 (cd /tmp && timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch_$TAG -o run --output-format csv \
