@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define SPEF_ABI_VERSION 3
+#define SPEF_ABI_VERSION 4
 #define SPEF_COMM_ID_BYTES 128   /* size of the RCCL unique id (ncclUniqueId) */
 
 enum spef_status {
@@ -105,6 +105,58 @@ int spef_set_decode_tables(spef_ctx* ctx, const double* ori_bins, int n_ori_bins
  * ori_soft / pos_soft may be NULL. */
 int spef_decode(spef_ctx* ctx, int ori_mode, int pos_mode, const float* ori_raw, int n_ori, const float* pos_raw,
                 int n_pos, int B, float* ori_soft, float* quat, float* pos_soft, float* pos, int* status, void* stream);
+
+/* Adaptive video filter on the device: the reference's TemporalPDF.update_pdf (src/temporal/pdf_compare.py:94-134)
+ * and the quaternion pole continuity of Inference.predict (src/temporal/inference.py:136-144, :173-180) for batches
+ * of video frames. Frames are TIME-MAJOR: a batch of T * S rows holds T consecutive time steps of S independent
+ * streams, row t * S + s = step t of stream s (T = 64, S = 1: 64 frames of one video; T = 1, S = 64: one new frame
+ * from each of 64 cameras). The state (previous filtered PDFs, poles) lives on the device; results do not depend on
+ * how a sequence is cut into calls.
+ *
+ * spef_video_create: a filter for n_streams streams with distance `metric` and TemporalPDF's (n, alpha) per head
+ *   (the reference's Inference engine: ori 0.8 / 16.49, pos 0.5 / 48.64, L2). The bin counts are those of the
+ *   context's decode tables, which must both be set (SPEF_ERR_STATE otherwise; spef_video_step returns
+ *   SPEF_ERR_STATE as well when the tables were replaced by ones of other sizes since). An unknown metric or
+ *   n_streams < 1: SPEF_ERR_ARG. Every stream starts reset. */
+enum spef_video_metric {   /* spef_amd.temporal.METRICS order */
+  SPEF_METRIC_L2 = 0,
+  SPEF_METRIC_KL = 1,
+  SPEF_METRIC_JS = 2,
+  SPEF_METRIC_HELLINGER = 3,
+  SPEF_METRIC_TV = 4,
+  SPEF_METRIC_WASSERSTEIN = 5
+};
+typedef struct spef_video spef_video;
+int spef_video_create(spef_ctx* ctx, int n_streams, int metric, float n_ori, float alpha_ori, float n_pos,
+                      float alpha_pos, spef_video** out);
+/* Forget the previous PDFs and poles of stream `stream` (or of all streams: -1): its next frame passes through with
+ * distance 0 and sets the poles. Enqueued on `stream_hip`; no host synchronisation. */
+int spef_video_reset(spef_video* video, int stream, void* stream_hip);
+/* Load the state of one stream from device memory (how spef_amd's Inference engine shares one filter between its
+ * per-frame host path and this one): ori_pdf [n_ori bins] / pos_pdf [n_pos bins] = the previous filtered PDFs,
+ * still_pole / video_pole [4] = the poles; a NULL pointer resets that part. Enqueued; no host synchronisation. */
+int spef_video_set_state(spef_video* video, int stream, const float* ori_pdf, const float* pos_pdf,
+                         const float* still_pole, const float* video_pole, void* stream_hip);
+/* One filter step over T time steps of all S streams (S must equal n_streams, T >= 1; SPEF_ERR_ARG otherwise, with
+ * nothing enqueued). ori_soft [T*S x n_ori bins] / pos_soft [T*S x n_pos bins] are spef_decode's soft outputs.
+ * Outputs: ori_filt / pos_filt = the filtered PDFs (same shapes; either may be NULL), ori_dist / pos_dist [T*S]
+ * = the distance of each frame to the stream's previous filtered PDF (0 on the first frame after a reset),
+ * quat [T*S x 4] / pos [T*S x 3] = the decode of the filtered PDFs (Markley average / soft-argmax, the kernels of
+ * spef_decode without their softmax), quat with the pole rule applied per stream in time order: negated when its dot
+ * product with the stream's pole is negative; the pole moves only when |dot| > 0.5; the first frame sets it.
+ * still_quat_inout (NULL, or spef_decode's quat [T*S x 4]) gets the same rule in place against the stream's
+ * still-frame pole. status [T*S]: written by this call, the bits of spef_decode (1 NaN orientation, 2 position zero
+ * sum, 4 NaN position).
+ * Bad frames: a frame whose input PDF does not sum to a positive finite number (all zero, a NaN in it) is passed to
+ * the decode unfiltered, so its status bits are set (all-zero orientation row: 1; all-zero position row: 2 and 4;
+ * NaN row: 1 / 4), its distance is NaN, and the stream's state is left as it was: the next good frame is filtered
+ * against the last good one. A blend that does not sum to a positive finite number (a NaN distance) is written
+ * out and flagged the same way and does not replace the state either.
+ * No allocation and no host synchronisation: it can follow spef_decode on a stream and be stream-captured. */
+int spef_video_step(spef_ctx* ctx, spef_video* video, const float* ori_soft, const float* pos_soft, int T, int S,
+                    float* still_quat_inout, float* ori_filt, float* ori_dist, float* pos_filt, float* pos_dist,
+                    float* quat, float* pos, int* status, void* stream_hip);
+int spef_video_destroy(spef_video* video);
 
 /* Keypoint mode (ORI == POS == 'keypoints', config.py:53-58): the 3-D model points (host float32 n x 3,
  * e.g. tangoPoints.mat's 11 Tango keypoints, keypoints_utils.py:31-45), the camera matrix (host float64

@@ -14,6 +14,7 @@
 
 #include "spef_common.hpp"
 #include "spef_kernels.hpp"
+#include "spef_reduce.hpp"
 
 namespace spef {
 
@@ -122,42 +123,7 @@ __global__ void fc_reduce_kernel(const float* __restrict__ part, const float* __
   out[(size_t)j * n + i] = v;
 }
 
-// ------------------------------------------------------------------------------------------ reductions
-// Workgroup (4 waves) max / sum of one float per thread: within a 16-lane row by DPP (quad swaps, half-row and row
-// mirrors: every lane ends with its row's value, no LDS round trip), the 4 rows by readlane, the 4 waves through
-// LDS with one barrier. sh[4] must not be reused by the caller. A fixed combination order: deterministic.
-template <bool MAX>
-__device__ __forceinline__ float dpp_op(float a, float b) { return MAX ? fmaxf(a, b) : a + b; }
-template <bool MAX, int CTRL>
-__device__ __forceinline__ float dpp_step(float v) {
-  const float o = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-  return dpp_op<MAX>(v, o);
-}
-template <bool MAX>
-__device__ __forceinline__ float block_reduce256(float v, float* sh) {
-  v = dpp_step<MAX, 0xB1>(v);    // quad_perm [1,0,3,2]
-  v = dpp_step<MAX, 0x4E>(v);    // quad_perm [2,3,0,1]
-  v = dpp_step<MAX, 0x141>(v);   // row_half_mirror
-  v = dpp_step<MAX, 0x140>(v);   // row_mirror
-  const int u = __builtin_bit_cast(int, v);
-  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(u, 0));
-  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(u, 16));
-  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(u, 32));
-  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(u, 48));
-  const float w = dpp_op<MAX>(dpp_op<MAX>(r0, r1), dpp_op<MAX>(r2, r3));
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
-  __syncthreads();
-  return dpp_op<MAX>(dpp_op<MAX>(sh[0], sh[1]), dpp_op<MAX>(sh[2], sh[3]));
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp_add_d(double v) {   // v + (v of the DPP source lane), fp64 as two dword moves
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xf, 0xf, false);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, false);
-  return v + __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ float block_max256(float v, float* sh) { return block_reduce256<true>(v, sh); }
-__device__ __forceinline__ float block_sum256(float v, float* sh) { return block_reduce256<false>(v, sh); }
+// (workgroup reductions: spef_reduce.hpp)
 
 // Top eigenvector of the symmetric PSD 4x4 a (fp64, packed upper triangle t) by repeated squaring: each step
 // M <- M^2 multiplies the eigenvalue ratios (l_i / l_1) by themselves, so after k steps M is l_1-dominated to
@@ -234,7 +200,10 @@ __device__ void sym4_top_eigvec(const double t[10], double out[4]) {
 // order).
 // It also writes the image's whole status word (the decode's first kernel: no memset launch) and, in position
 // regression mode, copies the 3 raw position outputs (no copy launch): pos_src == nullptr skips the copy.
-template <int PER>
+// PDF = true (the video path, k_video.hip): `logits` already holds a PDF (the filtered one), so the softmax is
+// skipped and p_i is the input itself; a row whose moments have no positive trace (all zero) is flagged like a NaN
+// one (the reference's decode of the 0 / 0 row raises the same error). PDF = false is the still-frame decode.
+template <int PER, bool PDF = false>
 __global__ __launch_bounds__(256) void decode_ori_kernel(const float* __restrict__ logits, int n,
                                                          const double* __restrict__ qb, float* __restrict__ soft,
                                                          float* __restrict__ quat, int* __restrict__ status,
@@ -250,7 +219,7 @@ __global__ __launch_bounds__(256) void decode_ori_kernel(const float* __restrict
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
     const int i = tid + 256 * j;
-    v[j] = i < n ? x[i] : -INFINITY;
+    v[j] = i < n ? x[i] : (PDF ? 0.0f : -INFINITY);
   }
   // the bin quaternions are loaded with the logits (PER <= 8: 64 VGPRs), not after the softmax: in the network the
   // forward has evicted them, and that second dependent HBM round trip was 40 % of the kernel (head_bench trace)
@@ -263,20 +232,23 @@ __global__ __launch_bounds__(256) void decode_ori_kernel(const float* __restrict
       qv[j] = *reinterpret_cast<const double4*>(qb + 4 * (i < n ? i : 0));
     }
   }
-  float m = v[0];
+  float s = 1.0f;
+  if constexpr (!PDF) {
+    float m = v[0];
 #pragma unroll
-  for (int j = 1; j < PER; ++j) m = fmaxf(m, v[j]);
-  SPEF_TRACE(1);
-  m = block_max256(m, shf[0]);
-  SPEF_TRACE(2);
-  float s = 0.0f;
+    for (int j = 1; j < PER; ++j) m = fmaxf(m, v[j]);
+    SPEF_TRACE(1);
+    m = block_max256(m, shf[0]);
+    SPEF_TRACE(2);
+    s = 0.0f;
 #pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    v[j] = tid + 256 * j < n ? expf(v[j] - m) : 0.0f;
-    s += v[j];
+    for (int j = 0; j < PER; ++j) {
+      v[j] = tid + 256 * j < n ? expf(v[j] - m) : 0.0f;
+      s += v[j];
+    }
+    s = block_sum256(s, shf[1]);
+    SPEF_TRACE(3);
   }
-  s = block_sum256(s, shf[1]);
-  SPEF_TRACE(3);
   double mom[10];
 #pragma unroll
   for (int k = 0; k < 10; ++k) mom[k] = 0.0;
@@ -284,8 +256,8 @@ __global__ __launch_bounds__(256) void decode_ori_kernel(const float* __restrict
   for (int j = 0; j < PER; ++j) {
     const int i = tid + 256 * j;
     if (i < n) {
-      const float p = v[j] / s;
-      if (soft) soft[(size_t)b * n + i] = p;
+      const float p = PDF ? v[j] : v[j] / s;
+      if (!PDF && soft) soft[(size_t)b * n + i] = p;
       const double pd = (double)p;
       double4 q;
       if constexpr (PF) q = qv[j];
@@ -321,6 +293,7 @@ __global__ __launch_bounds__(256) void decode_ori_kernel(const float* __restrict
     t[k] = shp[k][0];
     nan |= isnan(t[k]);
   }
+  if constexpr (PDF) nan |= !((t[0] + t[4]) + (t[7] + t[9]) > 0.0);
   status[b] = nan ? 1 : 0;
   if (nan) {  // classification_utils.py:134-135
     for (int k = 0; k < 4; ++k) quat[4 * b + k] = NAN;
@@ -334,6 +307,8 @@ __global__ __launch_bounds__(256) void decode_ori_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------ decode pos
+// PDF = true (the video path): `logits` is the filtered PDF itself, no softmax.
+template <bool PDF = false>
 __global__ __launch_bounds__(256) void decode_pos_kernel(const float* __restrict__ logits, int n,
                                                          const double* __restrict__ grid, float* __restrict__ soft,
                                                          float* __restrict__ pos, int* __restrict__ status) {
@@ -342,17 +317,20 @@ __global__ __launch_bounds__(256) void decode_pos_kernel(const float* __restrict
   __shared__ float shp[4];
   const int b = blockIdx.x;
   const float* x = logits + (size_t)b * n;
-  float m = -INFINITY;
-  for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, x[i]);
-  m = block_max256(m, shf[0]);
-  float s = 0.0f;
-  for (int i = threadIdx.x; i < n; i += 256) s += expf(x[i] - m);
-  s = block_sum256(s, shf[1]);
+  float m = 0.0f, s = 1.0f;
+  if constexpr (!PDF) {
+    m = -INFINITY;
+    for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, x[i]);
+    m = block_max256(m, shf[0]);
+    s = 0.0f;
+    for (int i = threadIdx.x; i < n; i += 256) s += expf(x[i] - m);
+    s = block_sum256(s, shf[1]);
+  }
   double acc[3] = {0.0, 0.0, 0.0};
   float ps = 0.0f;
   for (int i = threadIdx.x; i < n; i += 256) {
-    const float p = expf(x[i] - m) / s;
-    if (soft) soft[(size_t)b * n + i] = p;
+    const float p = PDF ? x[i] : expf(x[i] - m) / s;
+    if (!PDF && soft) soft[(size_t)b * n + i] = p;
     ps += p;
     const double pd = (double)p;
     acc[0] += grid[3 * i] * pd;
@@ -433,7 +411,19 @@ hipError_t launch_normalize_ori(const float* raw, int B, float* quat, int* statu
 
 hipError_t launch_decode_pos(const float* logits, int B, int n_bins, const double* grid, float* soft, float* pos,
                              int* status, hipStream_t s) {
-  decode_pos_kernel<<<B, 256, 0, s>>>(logits, n_bins, grid, soft, pos, status);
+  decode_pos_kernel<false><<<B, 256, 0, s>>>(logits, n_bins, grid, soft, pos, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_decode_pdf(const float* ori_pdf, const float* pos_pdf, int B, int n_ori, const double* q_bins,
+                             int n_pos, const double* grid, float* quat, float* pos, int* status, hipStream_t s) {
+  if (n_ori <= 256 * 8)
+    decode_ori_kernel<8, true><<<B, 256, 0, s>>>(ori_pdf, n_ori, q_bins, nullptr, quat, status, nullptr, nullptr);
+  else if (n_ori <= 256 * 32)
+    decode_ori_kernel<32, true><<<B, 256, 0, s>>>(ori_pdf, n_ori, q_bins, nullptr, quat, status, nullptr, nullptr);
+  else
+    return hipErrorInvalidValue;
+  decode_pos_kernel<true><<<B, 256, 0, s>>>(pos_pdf, n_pos, grid, nullptr, pos, status);
   return hipGetLastError();
 }
 

@@ -1501,6 +1501,144 @@ int spef_decode(spef_ctx* c, int ori_mode, int pos_mode, const float* ori_raw, i
   return SPEF_OK;
 }
 
+// ------------------------------------------------------------------------------------------ video filter
+struct spef_video {
+  int device = 0;
+  int S = 0, metric = 0;
+  int n_ori = 0, n_pos = 0;              // bin counts of the decode tables at creation
+  float nmix[2] = {0.f, 0.f}, alpha[2] = {0.f, 0.f};
+  float* state[2] = {nullptr, nullptr};  // [S][n] previous filtered PDFs (ori, pos)
+  float* state_sum = nullptr;            // [2][S]
+  int* flags = nullptr;                  // [4][S]: ori have, pos have, still pole have, video pole have
+  float* poles = nullptr;                // [2][S][4]: still, video
+  float* scratch[2] = {nullptr, nullptr};  // filtered PDFs of one chunk when the caller does not want them
+  int scratch_T = 0;
+};
+
+static VideoHead video_head(const spef_video* v, int k, const float* in, float* filt, float* dist) {
+  VideoHead h;
+  h.in = in;
+  h.filt = filt;
+  h.dist = dist;
+  h.state = v->state[k];
+  h.state_sum = v->state_sum + (size_t)k * v->S;
+  h.have = v->flags + (size_t)k * v->S;
+  h.n = k ? v->n_pos : v->n_ori;
+  h.nmix = v->nmix[k];
+  h.alpha = v->alpha[k];
+  return h;
+}
+
+int spef_video_destroy(spef_video* v) {
+  if (!v) return SPEF_OK;
+  Dev d(v->device);
+  for (int k = 0; k < 2; ++k) {
+    if (v->state[k]) hipFree(v->state[k]);
+    if (v->scratch[k]) hipFree(v->scratch[k]);
+  }
+  if (v->state_sum) hipFree(v->state_sum);
+  if (v->flags) hipFree(v->flags);
+  if (v->poles) hipFree(v->poles);
+  delete v;
+  return SPEF_OK;
+}
+
+int spef_video_create(spef_ctx* c, int n_streams, int metric, float n_ori, float alpha_ori, float n_pos,
+                      float alpha_pos, spef_video** out) {
+  if (!c || !out) return fail(SPEF_ERR_ARG, "null argument");
+  if (n_streams < 1) return fail(SPEF_ERR_ARG, "n_streams must be at least 1");
+  if (metric < VM_L2 || metric > VM_WASSERSTEIN) return fail(SPEF_ERR_ARG, "unknown distance metric");
+  if (!c->d_ori_bins || !c->d_pos_grid)
+    return fail(SPEF_ERR_STATE, "the video filter needs both decode tables (spef_set_decode_tables)");
+  Dev d(c->device);
+  spef_video* v = new spef_video;
+  v->device = c->device;
+  v->S = n_streams;
+  v->metric = metric;
+  v->n_ori = c->n_ori_bins;
+  v->n_pos = c->n_pos_bins;
+  v->nmix[0] = n_ori; v->alpha[0] = alpha_ori;
+  v->nmix[1] = n_pos; v->alpha[1] = alpha_pos;
+  // scratch: at least 64 rows, whole time steps
+  v->scratch_T = n_streams >= 64 ? 1 : 64 / n_streams;
+  const size_t S = (size_t)n_streams, rows = S * v->scratch_T;
+  hipError_t e = hipMalloc(&v->state[0], S * v->n_ori * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&v->state[1], S * v->n_pos * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&v->scratch[0], rows * v->n_ori * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&v->scratch[1], rows * v->n_pos * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&v->state_sum, 2 * S * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&v->flags, 4 * S * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&v->poles, 8 * S * sizeof(float));
+  if (e == hipSuccess) e = hipMemset(v->flags, 0, 4 * S * sizeof(int));
+  if (e == hipSuccess) e = hipMemset(v->state_sum, 0, 2 * S * sizeof(float));
+  if (e == hipSuccess) e = hipMemset(v->poles, 0, 8 * S * sizeof(float));
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    spef_video_destroy(v);
+    return fail(SPEF_ERR_HIP, std::string("spef_video_create: ") + hipGetErrorString(e));
+  }
+  *out = v;
+  return SPEF_OK;
+}
+
+int spef_video_reset(spef_video* v, int stream, void* stream_hip) {
+  if (!v) return fail(SPEF_ERR_ARG, "null video filter");
+  if (stream < -1 || stream >= v->S) return fail(SPEF_ERR_ARG, "stream index out of range");
+  Dev d(v->device);
+  HIP_TRY(launch_video_reset(v->flags, v->S, stream, (hipStream_t)stream_hip));
+  return SPEF_OK;
+}
+
+int spef_video_set_state(spef_video* v, int stream, const float* ori_pdf, const float* pos_pdf,
+                         const float* still_pole, const float* video_pole, void* stream_hip) {
+  if (!v) return fail(SPEF_ERR_ARG, "null video filter");
+  if (stream < 0 || stream >= v->S) return fail(SPEF_ERR_ARG, "stream index out of range");
+  Dev d(v->device);
+  HIP_TRY(launch_video_set_state(video_head(v, 0, nullptr, nullptr, nullptr), video_head(v, 1, nullptr, nullptr, nullptr),
+                                 v->poles, v->flags + 2 * (size_t)v->S, v->S, stream, ori_pdf, pos_pdf, still_pole,
+                                 video_pole, (hipStream_t)stream_hip));
+  return SPEF_OK;
+}
+
+int spef_video_step(spef_ctx* c, spef_video* v, const float* ori_soft, const float* pos_soft, int T, int S,
+                    float* still_quat, float* ori_filt, float* ori_dist, float* pos_filt, float* pos_dist, float* quat,
+                    float* pos, int* status, void* stream_hip) {
+  if (!c || !v) return fail(SPEF_ERR_ARG, "null context or video filter");
+  if (!ori_soft || !pos_soft || !ori_dist || !pos_dist || !quat || !pos || !status)
+    return fail(SPEF_ERR_ARG, "null argument");
+  if (S != v->S)
+    return fail(SPEF_ERR_ARG, "S = " + std::to_string(S) + ", the filter has " + std::to_string(v->S) + " streams");
+  if (T < 1) return fail(SPEF_ERR_ARG, "T must be at least 1");
+  if ((int64_t)T * S > 0x7fffffff) return fail(SPEF_ERR_ARG, "too many frames");
+  if (c->device != v->device) return fail(SPEF_ERR_ARG, "the filter belongs to another device");
+  if (!c->d_ori_bins || !c->d_pos_grid || c->n_ori_bins != v->n_ori || c->n_pos_bins != v->n_pos)
+    return fail(SPEF_ERR_STATE, "the decode tables changed since spef_video_create");
+  Dev d(c->device);
+  hipStream_t s = (hipStream_t)stream_hip;
+  // with both filtered-PDF outputs given: one scan, one decode over all T * S frames; otherwise chunks of
+  // scratch_T time steps through the filter's own buffers
+  const int Tc = (ori_filt && pos_filt) ? T : v->scratch_T;
+  for (int t0 = 0; t0 < T; t0 += Tc) {
+    const int tc = std::min(Tc, T - t0);
+    const size_t r0 = (size_t)t0 * S;
+    float* fo = ori_filt ? ori_filt + r0 * v->n_ori : v->scratch[0];
+    float* fp = pos_filt ? pos_filt + r0 * v->n_pos : v->scratch[1];
+    const VideoHead ho = video_head(v, 0, ori_soft + r0 * v->n_ori, fo, ori_dist + r0);
+    const VideoHead hp = video_head(v, 1, pos_soft + r0 * v->n_pos, fp, pos_dist + r0);
+    const double px = (double)tc * S * (v->n_ori + v->n_pos);
+    HIP_TRY(prof_launch(c, s, "video_scan_kernel", px * 12, px * 20,
+                        [&] { return launch_video_scan(ho, hp, tc, S, v->metric, s); }));
+    HIP_TRY(prof_launch(c, s, "decode_pdf_kernels", px * 4 + 32.0 * v->n_ori + 24.0 * v->n_pos, px * 30, [&] {
+      return launch_decode_pdf(fo, fp, tc * S, v->n_ori, c->d_ori_bins, v->n_pos, c->d_pos_grid, quat + r0 * 4,
+                               pos + r0 * 3, status + r0, s);
+    }));
+  }
+  HIP_TRY(prof_launch(c, s, "video_pole_kernel", (double)T * S * 64, 0.0, [&] {
+    return launch_video_pole(quat, still_quat, v->poles, v->flags + 2 * (size_t)v->S, T, S, s);
+  }));
+  return SPEF_OK;
+}
+
 int spef_set_keypoints(spef_ctx* c, const float* kp3d, int n, const double* K, float nu, float nv) {
   if (!c || !kp3d || !K || n < 4 || n > 16) return fail(SPEF_ERR_ARG, "bad keypoint configuration");
   Dev d(c->device);

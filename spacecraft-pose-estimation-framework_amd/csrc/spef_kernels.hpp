@@ -153,6 +153,37 @@ hipError_t launch_normalize_ori(const float* raw, int B, float* quat, int* statu
 hipError_t launch_decode_pos(const float* logits, int B, int n_bins, const double* grid, float* soft,
                              float* pos, int* status, hipStream_t s);
 
+// The same decodes of rows that already are PDFs (the video path's filtered PDFs: no softmax). The orientation
+// kernel writes status[b] (a row without positive moment trace counts as NaN: bit 1), the position kernel ORs 2 / 4.
+hipError_t launch_decode_pdf(const float* ori_pdf, const float* pos_pdf, int B, int n_ori, const double* q_bins,
+                             int n_pos, const double* grid, float* quat, float* pos, int* status, hipStream_t s);
+
+// ---- adaptive video filter (k_video.hip; TemporalPDF.update_pdf, src/temporal/pdf_compare.py:94-134) ----
+// Frames are time-major: row t * S + s is time step t of stream s. One head (ori or pos) of the filter:
+struct VideoHead {
+  const float* in;    // [T][S][n] soft-classification PDFs
+  float* filt;        // [T][S][n] filtered PDFs
+  float* dist;        // [T][S] distance to the previous filtered PDF (0 on a stream's first frame)
+  float* state;       // [S][n] previous filtered PDF per stream
+  float* state_sum;   // [S] its sum (fp64 sum rounded to float32)
+  int* have;          // [S] 0 after a reset: the next frame passes through
+  int n;              // bins (<= 8192)
+  float nmix, alpha;  // TemporalPDF n and alpha
+};
+enum VideoMetric : int { VM_L2 = 0, VM_KL = 1, VM_JS = 2, VM_HELLINGER = 3, VM_TV = 4, VM_WASSERSTEIN = 5 };
+// Sequential scan over t of both heads, one workgroup per (stream, head).
+hipError_t launch_video_scan(const VideoHead& ori, const VideoHead& pos, int T, int S, int metric, hipStream_t s);
+// Quaternion pole continuity per stream in time order (src/temporal/inference.py:136-144): quat_video / quat_still
+// [T][S][4] in place (either may be null); poles [2][S][4] and pole_have [2][S]: 0 = still, 1 = video.
+hipError_t launch_video_pole(float* quat_video, float* quat_still, float* poles, int* pole_have, int T, int S,
+                             hipStream_t s);
+// flags [4][S] (ori have, pos have, still pole have, video pole have): clear stream `stream`, or all with -1.
+hipError_t launch_video_reset(int* flags, int S, int stream, hipStream_t s);
+// Load one stream's state from device rows (a null pointer clears that part).
+hipError_t launch_video_set_state(const VideoHead& ori, const VideoHead& pos, float* poles, int* pole_have, int S,
+                                  int stream, const float* ori_pdf, const float* pos_pdf, const float* still_pole,
+                                  const float* video_pole, hipStream_t s);
+
 // ---- INT8 path (k_q8.hip; integer semantics of oracle/int8_ref.py) ----
 enum QEpi : int { QEPI_RELU = 0, QEPI_PROJ = 1, QEPI_PROJ_RES = 2, QEPI_FC = 3 };
 

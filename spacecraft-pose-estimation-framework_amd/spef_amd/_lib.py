@@ -12,8 +12,9 @@ from . import _build
 OK, ERR_ARG, ERR_HIP, ERR_BLOB, ERR_STATE, ERR_NUMERIC, ERR_COMM = range(7)
 IN_U8_NHWC, IN_F32_NCHW = 0, 1
 REGRESSION, CLASSIFICATION, KEYPOINTS = 0, 1, 2
-ABI_VERSION = 3
+ABI_VERSION = 4
 COMM_ID_BYTES = 128
+METRIC_IDS = {'l2': 0, 'kl': 1, 'js': 2, 'hellinger': 3, 'tv': 4, 'wasserstein': 5}   # spef_video_metric
 OPT_FUSE_BLOCKS, OPT_WAVESPEC, OPT_Q8_ROLESPLIT = 1, 6, 7     # public schedule options (include/spef.h)
 OPT_FUSE_MIN_HW, OPT_PW_GEMM, OPT_IRB_VARIANT, OPT_TEST_FAIL_BCAST = 2, 3, 4, 5   # internal (csrc/spef_tuning.hpp)
 OPT_MX_KERNELS = 8   # internal: fp16mx blocks 2-7 on k_mx.hip (1) or the fp16x2 slab kernels (0)
@@ -36,6 +37,11 @@ SIGNATURES = {
     'spef_probe': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _ip, _ip, _ip, _vp]),
     'spef_set_decode_tables': (_i, [_vp, _vp, _i, _vp, _i]),
     'spef_decode': (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'spef_video_create': (_i, [_vp, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(_vp)]),
+    'spef_video_reset': (_i, [_vp, _i, _vp]),
+    'spef_video_set_state': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    'spef_video_step': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'spef_video_destroy': (_i, [_vp]),
     'spef_validate_blob': (_i, [_vp, _sz, _ip, _ip, _ip, _ip]),
     'spef_comm_unique_id': (_i, [_vp, _sz]),
     'spef_comm_init': (_i, [_i, _i, _i, _vp, _i, C.POINTER(_vp)]),

@@ -22,6 +22,84 @@ def _stream(device: torch.device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+class VideoFilter:
+    """Device state of the adaptive video filter for ``n_streams`` streams (``Engine.video_filter``).
+
+    Frames are time-major: a batch of ``T * n_streams`` rows holds T consecutive time steps of every stream, row
+    ``t * n_streams + s`` = step t of stream s. ``step`` only enqueues kernels on the current stream (no
+    allocation in the library, no host sync), so it can follow ``Engine.decode`` and be captured in a HIP graph."""
+
+    def __init__(self, engine: 'Engine', n_streams: int, metric: str = 'l2', n_ori: float = 0.8,
+                 alpha_ori: float = 16.49, n_pos: float = 0.5, alpha_pos: float = 48.64):
+        self.engine = engine
+        self.lib = engine.lib
+        self.device = engine.device
+        self.n_streams = int(n_streams)
+        self.metric = metric.lower()
+        h = C.c_void_p()
+        L.check(self.lib.spef_video_create(engine.ctx, self.n_streams, L.METRIC_IDS.get(self.metric, -1), n_ori,
+                                           alpha_ori, n_pos, alpha_pos, C.byref(h)))
+        self.handle = h
+        self.last_event = None   # StreamPipeline: the event after the last step it enqueued (steps serialise)
+
+    def step(self, dec: dict, T: int, engine: Optional['Engine'] = None, want_filtered: bool = True) -> dict:
+        """``dec``: what ``Engine.decode(..., want_soft=True)`` returned for ``T * n_streams`` time-major frames.
+        -> {'ori', 'pos', 'ori_soft', 'pos_soft', 'ori_distance', 'pos_distance', 'status'} of the filtered frames
+        (device tensors). ``dec['ori']`` (the still quaternions) gets the pole rule in place. ``engine``: the
+        context whose decode tables are used (default: the one the filter was made from; ``StreamPipeline`` passes
+        the slot's)."""
+        eng = engine or self.engine
+        ori_soft, pos_soft, still = dec['ori_soft'], dec['pos_soft'], dec['ori']
+        assert ori_soft is not None and pos_soft is not None, 'the video filter needs both soft outputs'
+        B, S = ori_soft.shape[0], self.n_streams
+        assert T >= 1 and B == T * S, f'{B} frames are not T = {T} steps of {S} streams'
+        assert pos_soft.shape[0] == B and still.shape == (B, 4)
+        for t in (ori_soft, pos_soft, still):
+            assert t.device == self.device and t.is_contiguous() and t.dtype == torch.float32
+        dev = self.device
+        of = torch.empty_like(ori_soft) if want_filtered else None
+        pf = torch.empty_like(pos_soft) if want_filtered else None
+        od = torch.empty((B,), dtype=torch.float32, device=dev)
+        pd = torch.empty((B,), dtype=torch.float32, device=dev)
+        quat = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        pos = torch.empty((B, 3), dtype=torch.float32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        L.check(self.lib.spef_video_step(eng.ctx, self.handle, _ptr(ori_soft), _ptr(pos_soft), T, S, _ptr(still),
+                                         _ptr(of), _ptr(od), _ptr(pf), _ptr(pd), _ptr(quat), _ptr(pos), _ptr(status),
+                                         _stream(dev)))
+        return {'ori': quat, 'pos': pos, 'ori_soft': of, 'pos_soft': pf, 'ori_distance': od, 'pos_distance': pd,
+                'status': status}
+
+    def reset(self, stream: Optional[int] = None) -> None:
+        """Forget one stream's previous PDFs and poles (all streams: None); enqueued on the current stream."""
+        L.check(self.lib.spef_video_reset(self.handle, -1 if stream is None else int(stream), _stream(self.device)))
+
+    def set_state(self, stream: int, ori_pdf=None, pos_pdf=None, still_pole=None, video_pole=None) -> None:
+        """Load one stream's state (NumPy arrays or tensors; None resets that part)."""
+        ts = [None if a is None else torch.as_tensor(np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a,
+                                                                 np.float32)).to(self.device).contiguous()
+              for a in (ori_pdf, pos_pdf, still_pole, video_pole)]
+        ob, pg = self.engine._decode_tables
+        for t, want in zip(ts, (ob.shape[0], pg.shape[0], 4, 4)):
+            assert t is None or t.numel() == want, f'state row of {t.numel()} values, expected {want}'
+        L.check(self.lib.spef_video_set_state(self.handle, int(stream), *[_ptr(t) for t in ts], _stream(self.device)))
+        for t in ts:
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(self.device))
+
+    def close(self) -> None:
+        if getattr(self, 'handle', None):
+            torch.cuda.synchronize(self.device)
+            self.lib.spef_video_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """Loaded weights + workspace on one GPU.
 
@@ -161,6 +239,13 @@ class Engine:
                                      pos_raw.shape[1], B, _ptr(ori_soft), _ptr(quat), _ptr(pos_soft), _ptr(pos),
                                      _ptr(status), _stream(dev)))
         return {'ori': quat, 'pos': pos, 'ori_soft': ori_soft, 'pos_soft': pos_soft, 'status': status}
+
+    def video_filter(self, n_streams: int, metric: str = 'l2', n_ori: float = 0.8, alpha_ori: float = 16.49,
+                     n_pos: float = 0.5, alpha_pos: float = 48.64) -> 'VideoFilter':
+        """The adaptive video filter (``TemporalPDF.update_pdf`` + pole continuity) for ``n_streams`` independent
+        streams on this engine's device; the defaults are the reference ``Inference`` engine's (inference.py:38-39).
+        Needs both decode tables."""
+        return VideoFilter(self, n_streams, metric, n_ori, alpha_ori, n_pos, alpha_pos)
 
     def set_fused(self, on: bool) -> None:
         """Fused inverted-residual blocks (default) or one kernel per conv (reference schedule)."""

@@ -11,6 +11,9 @@ on the new target. The reference's own devices can be served through ``engine_fa
 previous still frame (:136-144), keypoints / bounding box for visualisation (:146-155), and the optional
 'Adaptative' video filter (:158-190) -- whose filtered PDFs are decoded on the GPU (``Engine.decode`` on
 ``log(pdf)``: its softmax returns the PDF).
+
+``predict_sequence`` is the same loop for T consecutive frames of one video in one call: one batched forward, one
+decode and one video-filter step on the device (csrc/k_video.hip), sharing its state with ``predict``.
 """
 from __future__ import annotations
 
@@ -114,6 +117,70 @@ class Inference:
         if st.any():
             raise ValueError('Weighted PDF contains NaN or sums to zero')   # classification_utils.py:134-135, 253
         return dec['ori'][0].cpu().numpy(), dec['pos'][0].cpu().numpy()
+
+    @staticmethod
+    def _advance_pole(pole, quats: np.ndarray):
+        """The pole after a run of quaternions that already follow it (the rule of ``predict``; no flips left)."""
+        for q in quats:
+            if pole is None or np.abs(np.dot(pole, q)) > 0.5:
+                pole = q
+        return pole
+
+    def predict_sequence(self, images: torch.Tensor, video_type: Optional[str] = 'Adaptative') -> list:
+        """``images`` [T, 3, H, W]: T consecutive frames of one video -> the list of T ``(pose_still, latency_ms,
+        pose_video)`` triples that T calls of ``predict(images[t:t+1], video_type)`` return (keypoints and bounding
+        box included), computed with one batched forward, one decode and one video-filter step on the GPU
+        (``SPEMi355x.predict_video``; each frame is given latency / T). The reference runs this loop at batch 1
+        (temporal.py:102). The state is the one ``predict`` uses: it is loaded into the device filter before the
+        step and read back after it, so ``reset()`` clears both and the two calls can be mixed on one video.
+        An engine without ``predict_video`` (one of the reference's own, through ``engine_factories``) is driven
+        frame by frame."""
+        if video_type is not None and video_type != 'Adaptative':
+            raise ValueError(f'type of video filtering not implemented: {video_type}')
+        eng = self.inference_engine
+        T = int(images.shape[0])
+        if not hasattr(eng, 'predict_video'):
+            return [self.predict(images[t:t + 1], video_type) for t in range(T)]
+        self.img_size = (1,) + tuple(images.size())[1:]
+        fo, fp = self.pdf_adapt_ori, self.pdf_adapt_pos
+        video = None
+        if video_type is None:
+            still, latency_ms = eng.predict(images)
+            still = dict(still)
+            ori = np.array(still['ori'], copy=True)
+            for t in range(T):                       # the pole rule of predict, on the host
+                if self.prev_still_ori is None:
+                    self.prev_still_ori = ori[t]
+                    continue
+                dot = np.dot(self.prev_still_ori, ori[t])
+                if dot < 0:
+                    ori[t] = -ori[t]
+                if np.abs(dot) > 0.5:
+                    self.prev_still_ori = ori[t]
+            still['ori'] = ori
+        else:
+            assert self.spe_utils.ori_mode == 'classification'
+            assert self.spe_utils.pos_mode == 'classification'
+            if fo.distance_metric != fp.distance_metric:
+                raise ValueError('the device filter uses one distance metric for both heads')
+            params = dict(n_ori=fo.n, alpha_ori=fo.alpha, n_pos=fp.n, alpha_pos=fp.alpha)
+            vf = eng.video_filter(1, fo.distance_metric, **params)
+            vf.set_state(0, fo.previous_pdf, fp.previous_pdf, self.prev_still_ori, self.prev_video_ori)
+            still, video, latency_ms = eng.predict_video(images, 1, fo.distance_metric, **params)
+            fo.previous_pdf = np.array(video['ori_soft'][-1], copy=True)
+            fp.previous_pdf = np.array(video['pos_soft'][-1], copy=True)
+            self.prev_still_ori = self._advance_pole(self.prev_still_ori, still['ori'])
+            self.prev_video_ori = self._advance_pole(self.prev_video_ori, video['ori'])
+        out = []
+        for t in range(T):
+            pose_still = {k: v[t] for k, v in still.items()}
+            self._visual(pose_still)
+            pose_video = None
+            if video is not None:
+                pose_video = {k: v[t] for k, v in video.items()}
+                self._visual(pose_video)
+            out.append((pose_still, latency_ms / T, pose_video))
+        return out
 
     def predict(self, image: torch.Tensor, video_type: str = None) -> Tuple[dict, float, Optional[dict]]:
         """inference.py:117-191: -> (pose of the still frame, latency ms, filtered video pose or None)."""

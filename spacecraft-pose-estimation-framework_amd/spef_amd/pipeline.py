@@ -62,9 +62,15 @@ class StreamPipeline:
             e.reserve(B, H, W)
 
     def submit(self, frames: torch.Tensor, ori_mode: int = L.CLASSIFICATION, pos_mode: int = L.REGRESSION,
-               want_soft: bool = True) -> dict:
+               want_soft: bool = True, video=None) -> dict:
         """Enqueue forward + decode of one batch on the next stream; returns the decode dict (device tensors,
-        valid once that stream reaches them -- ``synchronize()`` or the dict's 'event')."""
+        valid once that stream reaches them -- ``synchronize()`` or the dict's 'event').
+
+        ``video``: a ``VideoFilter`` (``Engine.video_filter``) whose streams this batch holds, time-major (T *
+        n_streams frames, classification heads, ``want_soft``). Its step is enqueued on the slot's stream after the
+        decode -- outside the slot's recorded graph -- and ordered after the previous submit's step by an event:
+        the forwards of the slots still overlap, only the filter steps serialise. The filtered result is the
+        dict's 'video' entry (``VideoFilter.step``), and 'event' then covers it too."""
         i = self._next
         self._next = (i + 1) % self.depth
         eng, s = self.engines[i], self.streams[i]
@@ -76,16 +82,29 @@ class StreamPipeline:
             self._bufs[i] = buf
             self._drop_graphs(i)                                 # recorded against the previous buffers
         s.wait_stream(torch.cuda.current_stream(self.device))   # frames were produced on the caller's stream
+        if video is not None:
+            assert ori_mode == L.CLASSIFICATION and pos_mode == L.CLASSIFICATION and want_soft, \
+                'the video filter needs both soft PDFs'
+            assert B % video.n_streams == 0, f'{B} frames are not whole time steps of {video.n_streams} streams'
         if self.graphs:
-            return self._submit_graph(i, eng, s, buf, frames, ori_mode, pos_mode, want_soft)
-        with torch.cuda.stream(s):
-            frames.record_stream(s)
-            raw0, raw1 = eng.forward(frames, *buf)
-            dec = eng.decode(ori_mode, pos_mode, raw0, raw1, want_soft=want_soft)
-            ev = torch.cuda.Event()
-            ev.record(s)
-        dec['raw0'], dec['raw1'] = raw0, raw1
-        dec['event'] = ev
+            dec = self._submit_graph(i, eng, s, buf, frames, ori_mode, pos_mode, want_soft)
+        else:
+            with torch.cuda.stream(s):
+                frames.record_stream(s)
+                raw0, raw1 = eng.forward(frames, *buf)
+                dec = eng.decode(ori_mode, pos_mode, raw0, raw1, want_soft=want_soft)
+                ev = torch.cuda.Event()
+                ev.record(s)
+            dec['raw0'], dec['raw1'] = raw0, raw1
+            dec['event'] = ev
+        if video is not None:
+            with torch.cuda.stream(s):
+                if video.last_event is not None:
+                    s.wait_event(video.last_event)       # the filter's state: steps in submit order
+                dec['video'] = video.step(dec, B // video.n_streams, engine=eng)
+                ev = torch.cuda.Event()
+                ev.record(s)
+            video.last_event = dec['event'] = ev
         return dec
 
     def _drop_graphs(self, i: int) -> None:

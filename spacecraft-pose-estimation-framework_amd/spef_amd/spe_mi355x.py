@@ -40,6 +40,7 @@ class SPEMi355x:
         self.spe_utils = spe_utils
         self.device = torch.device(device)
         self.engine = None
+        self._video = None          # (configuration, VideoFilter) of predict_video
         self.update_model(model, self.device)
 
     # ------------------------------------------------------------------ lifecycle (spe_torch.py:78-124)
@@ -81,6 +82,7 @@ class SPEMi355x:
                                  f'{(want0, want1)}')
 
     def delete_model(self) -> None:
+        self._close_video()
         if self.engine is not None:
             self.engine.close()
         self.engine = None
@@ -125,6 +127,52 @@ class SPEMi355x:
         end.synchronize()
         latency_ms = start.elapsed_time(end) / max(1, num_predict)
         return self._pose(dec), latency_ms
+
+    # ------------------------------------------------------------------ video
+    def video_filter(self, n_streams: int = 1, metric: str = 'l2', **params):
+        """The engine's ``VideoFilter`` for this configuration (created on first use, kept with its state until
+        the configuration changes or the model is deleted). ``params``: n_ori, alpha_ori, n_pos, alpha_pos."""
+        key = (int(n_streams), metric.lower(), tuple(sorted(params.items())))
+        if self._video is None or self._video[0] != key:
+            self._close_video()
+            self._video = (key, self.engine.video_filter(n_streams, metric, **params))
+        return self._video[1]
+
+    def _close_video(self) -> None:
+        if getattr(self, '_video', None) is not None:
+            self._video[1].close()
+        self._video = None
+
+    def predict_video(self, images: torch.Tensor, n_streams: int = 1, metric: str = 'l2',
+                      **params) -> Tuple[Dict, Dict, float]:
+        """Time-major video frames ``images`` [T * n_streams, 3, H, W] (row t * n_streams + s = step t of stream
+        s) -> (still pose, video pose, latency ms): one batched forward, one decode and one video-filter step, all
+        on the GPU. Both are batched NumPy dicts with the keys of ``Inference.predict``: the still pose has 'ori',
+        'pos', 'ori_soft', 'pos_soft'; the video pose adds 'ori_distance' / 'pos_distance' and holds the filtered
+        PDFs and their decode. The quaternions of both follow their stream's pole (inference.py:136-144). The
+        filter's state persists between calls (``video_filter(...).reset()`` starts new videos)."""
+        if self.engine is None:
+            raise AssertionError('no model loaded')
+        if self.ori_mode != L.CLASSIFICATION or self.pos_mode != L.CLASSIFICATION:
+            raise AssertionError('the video filter needs classification heads (soft PDFs)')   # inference.py:161-162
+        x = images.to(self.device, non_blocking=True).contiguous()
+        B = x.shape[0]
+        if n_streams < 1 or B % n_streams:
+            raise AssertionError(f'{B} frames are not whole time steps of {n_streams} streams')
+        vf = self.video_filter(n_streams, metric, **params)
+        torch.cuda.synchronize(self.device)
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        _, _, dec = self._run(x)
+        vid = vf.step(dec, B // n_streams)
+        end.record()
+        end.synchronize()
+        still = self._pose(dec)
+        if np.any(vid['status'].cpu().numpy()):
+            raise ValueError('Weighted PDF contains NaN or sums to zero')   # classification_utils.py:134-135, 253
+        video = {k: vid[k].cpu().numpy() for k in ('ori', 'pos', 'ori_soft', 'pos_soft', 'ori_distance',
+                                                   'pos_distance')}
+        return still, video, start.elapsed_time(end)
 
     def _pose(self, dec) -> Dict:
         status = dec['status'].cpu().numpy()
