@@ -158,6 +158,70 @@ int spef_video_step(spef_ctx* ctx, spef_video* video, const float* ori_soft, con
                     float* quat, float* pos, int* status, void* stream_hip);
 int spef_video_destroy(spef_video* video);
 
+/* Pose scoring on the device: SPEUtils.get_score (src/spe/spe_utils.py:103-159), the per-image error lists of
+ * evaluation() with their std and median absolute deviation (src/tools/evaluation.py:59-99) and the per-video min /
+ * max / median / mean / std of the temporal tool (temporal.py:27-48), for poses that stay on the device. Rows are
+ * TIME-MAJOR as on the video path: row t * S + s belongs to group s (a video, a camera, or the one group of a plain
+ * evaluation). A scorer keeps one log of `capacity` rows per (group, track); a track is one kind of pose (track 0 the
+ * still poses, track 1 the filtered ones). Arithmetic (spef_amd/score.py states it in NumPy): float32 elementwise,
+ * every sum fp64 in a fixed order, acos / sqrt in fp64 rounded to float32; results do not depend on how the rows are
+ * cut into steps.
+ *
+ * One log row holds five float32: pos_err = |t_true - t|, pos_norm = pos_err / |t_true|, ori_rad = 2 acos(min(|q .
+ * q_true|, 1)), ori_deg = ori_rad * 180 / pi, ori_stable = 2 atan2(|q - s q_true|, |q + s q_true|) in fp64 with s =
+ * sign(q . q_true) (radians: the angle between the two unit quaternions, half the rotation angle, the form the parity
+ * checks use; it resolves small angles, where the acos form stops at about 0.04 degrees). Row flags:
+ * 1 = |q . q_true| > 1.01 (get_score raises ValueError there, spe_utils.py:137), 2 = a non-finite input, 4 =
+ * |t_true| == 0, 8 = the row's decode status is nonzero. A flagged row is logged as NaN, counts in n_bad and enters no
+ * statistic.
+ *
+ * spef_score_create: allocates the logs (n_groups, n_tracks, capacity >= 1, capacity <= 2^20; SPEF_ERR_ARG otherwise).
+ *   The context is used for its device and its profiler and must outlive the scorer. Every log starts empty. */
+#define SPEF_SCORE_FIELDS 19
+enum spef_score_field {   /* spef_score_finalize's doubles per (group, track), in this order */
+  SPEF_SCORE_N = 0,         /* good rows                                                                   */
+  SPEF_SCORE_N_BAD,         /* flagged rows in the log                                                     */
+  SPEF_SCORE_N_DROPPED,     /* rows that arrived after the log was full                                    */
+  SPEF_SCORE_ORI_SCORE,     /* mean ori_rad            (get_score 'ori_score')                             */
+  SPEF_SCORE_POS_SCORE,     /* mean pos_norm           ('pos_score')                                       */
+  SPEF_SCORE_ESA_SCORE,     /* their sum               ('esa_score')                                       */
+  SPEF_SCORE_ORI_ERROR,     /* ori_score * 180 / pi    ('ori_error', degrees)                              */
+  SPEF_SCORE_POS_ERROR,     /* mean pos_err            ('pos_error', metres)                               */
+  SPEF_SCORE_ORI_STD,       /* population std of ori_deg / pos_err, two passes in fp64                     */
+  SPEF_SCORE_POS_STD,
+  SPEF_SCORE_ORI_MEDIAN,    /* np.median of the float32 ori_deg / pos_err: the middle one or (a + b) * 0.5 */
+  SPEF_SCORE_POS_MEDIAN,
+  SPEF_SCORE_ORI_MAD,       /* median of float32 |x - median| (mad(), evaluation.py:16-32)                 */
+  SPEF_SCORE_POS_MAD,
+  SPEF_SCORE_ORI_MIN,
+  SPEF_SCORE_ORI_MAX,
+  SPEF_SCORE_POS_MIN,
+  SPEF_SCORE_POS_MAX,
+  SPEF_SCORE_FLAGS          /* OR of the flags of every row in the log                                     */
+};
+typedef struct spef_score spef_score;
+int spef_score_create(spef_ctx* ctx, int n_groups, int n_tracks, int capacity, spef_score** out);
+/* Empty the logs of group `group` (all groups: -1) in every track. Enqueued; no host synchronisation. */
+int spef_score_reset(spef_score* score, int group, void* stream);
+/* Score T time steps of all S groups (S must equal n_groups, T >= 1, 0 <= track < n_tracks; SPEF_ERR_ARG otherwise,
+ * with nothing enqueued) and append them to the logs of `track`: row t * S + s goes to slot count[s] + t of group s,
+ * the counts are read and advanced on the device. quat [T*S x 4] / pos [T*S x 3] = the predicted poses (spef_decode's
+ * or spef_video_step's outputs), status (or NULL) [T*S] their decode status, quat_true / pos_true the targets.
+ * rows_out (or NULL) [T*S x 5] receives the rows as well. A row that arrives when its log is full is not stored and is
+ * counted in n_dropped. No allocation and no host synchronisation: it can follow spef_decode / spef_video_step on a
+ * stream and be stream-captured. */
+int spef_score_step(spef_score* score, int track, const float* quat, const float* pos, const int* status,
+                    const float* quat_true, const float* pos_true, int T, int S, float* rows_out, void* stream);
+/* The statistics of every (group, track) over its good rows: stats (device) receives n_groups * n_tracks *
+ * SPEF_SCORE_FIELDS doubles, (group, track) major. With no good row every statistic is NaN. The logs are only read:
+ * scoring can go on afterwards. The order statistics are exact (a sort of a scratch copy, in LDS up to 8192 rows).
+ * No allocation and no host synchronisation. */
+int spef_score_finalize(spef_score* score, double* stats, void* stream);
+/* Copy n log slots starting at `first` of (track, group) to device buffers rows [n x 5] / flags [n] (first + n <=
+ * capacity; slots at or past the group's count hold stale data). Enqueued; no host synchronisation. */
+int spef_score_log(spef_score* score, int track, int group, int first, int n, float* rows, int* flags, void* stream);
+int spef_score_destroy(spef_score* score);
+
 /* Keypoint mode (ORI == POS == 'keypoints', config.py:53-58): the 3-D model points (host float32 n x 3,
  * e.g. tangoPoints.mat's 11 Tango keypoints, keypoints_utils.py:31-45), the camera matrix (host float64
  * 3x3 row-major) and the image size the keypoints are normalised by (Camera nu, nv; speed.py:18-32). */

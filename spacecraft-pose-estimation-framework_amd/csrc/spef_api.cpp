@@ -1639,6 +1639,116 @@ int spef_video_step(spef_ctx* c, spef_video* v, const float* ori_soft, const flo
   return SPEF_OK;
 }
 
+// ------------------------------------------------------------------------------------------ pose scoring
+static_assert(SPEF_SCORE_FIELDS == SCORE_FIELDS && (int)SPEF_SCORE_FLAGS == (int)SF_FLAGS &&
+                  (int)SPEF_SCORE_POS_MAX == (int)SF_POS_MAX,
+              "spef_score_field and spef::ScoreField must agree");
+
+struct spef_score {
+  spef_ctx* ctx = nullptr;   // profiler of the step / finalize launches
+  int device = 0;
+  int n_tracks = 0;
+  ScoreLog log{};
+  float* scratch = nullptr;  // the sort's copies when the capacity exceeds one LDS tile
+  unsigned scratch_stride = 0;
+};
+
+int spef_score_destroy(spef_score* sc) {
+  if (!sc) return SPEF_OK;
+  Dev d(sc->device);   // not through ctx: the context may be gone already
+  if (sc->log.rows) hipFree(sc->log.rows);
+  if (sc->log.flags) hipFree(sc->log.flags);
+  if (sc->log.count) hipFree(sc->log.count);
+  if (sc->log.dropped) hipFree(sc->log.dropped);
+  if (sc->scratch) hipFree(sc->scratch);
+  delete sc;
+  return SPEF_OK;
+}
+
+int spef_score_create(spef_ctx* c, int n_groups, int n_tracks, int capacity, spef_score** out) {
+  if (!c || !out) return fail(SPEF_ERR_ARG, "null argument");
+  if (n_groups < 1 || n_tracks < 1 || capacity < 1)
+    return fail(SPEF_ERR_ARG, "n_groups, n_tracks and capacity must be at least 1");
+  if (capacity > (1 << 20)) return fail(SPEF_ERR_ARG, "capacity above 2^20 rows per group");
+  if ((int64_t)n_groups * n_tracks > (1 << 16)) return fail(SPEF_ERR_ARG, "more than 65536 (group, track) logs");
+  Dev d(c->device);
+  spef_score* sc = new spef_score;
+  sc->ctx = c;
+  sc->device = c->device;
+  sc->n_tracks = n_tracks;
+  sc->log.n_groups = n_groups;
+  sc->log.capacity = capacity;
+  const size_t logs = (size_t)n_groups * n_tracks, slots = logs * capacity;
+  hipError_t e = hipMalloc(&sc->log.rows, slots * 5 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&sc->log.flags, slots * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&sc->log.count, logs * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&sc->log.dropped, logs * sizeof(long long));
+  if (e == hipSuccess && (unsigned)capacity > SCORE_TILE) {
+    unsigned p = SCORE_TILE;
+    while (p < (unsigned)capacity) p <<= 1;
+    sc->scratch_stride = p;
+    e = hipMalloc(&sc->scratch, logs * 2 * p * sizeof(float));
+  }
+  if (e == hipSuccess) e = hipMemset(sc->log.count, 0, logs * sizeof(int));
+  if (e == hipSuccess) e = hipMemset(sc->log.dropped, 0, logs * sizeof(long long));
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    spef_score_destroy(sc);
+    return fail(SPEF_ERR_HIP, std::string("spef_score_create: ") + hipGetErrorString(e));
+  }
+  *out = sc;
+  return SPEF_OK;
+}
+
+int spef_score_reset(spef_score* sc, int group, void* stream) {
+  if (!sc) return fail(SPEF_ERR_ARG, "null scorer");
+  if (group < -1 || group >= sc->log.n_groups) return fail(SPEF_ERR_ARG, "group index out of range");
+  Dev d(sc->device);
+  HIP_TRY(launch_score_reset(sc->log, sc->n_tracks, group, (hipStream_t)stream));
+  return SPEF_OK;
+}
+
+int spef_score_step(spef_score* sc, int track, const float* quat, const float* pos, const int* status,
+                    const float* quat_true, const float* pos_true, int T, int S, float* rows_out, void* stream) {
+  if (!sc) return fail(SPEF_ERR_ARG, "null scorer");
+  if (!quat || !pos || !quat_true || !pos_true) return fail(SPEF_ERR_ARG, "null argument");
+  if (track < 0 || track >= sc->n_tracks) return fail(SPEF_ERR_ARG, "track index out of range");
+  if (S != sc->log.n_groups)
+    return fail(SPEF_ERR_ARG, "S = " + std::to_string(S) + ", the scorer has " + std::to_string(sc->log.n_groups) +
+                                  " groups");
+  if (T < 1) return fail(SPEF_ERR_ARG, "T must be at least 1");
+  if ((int64_t)T * S > 0x7fffffff) return fail(SPEF_ERR_ARG, "too many rows");
+  spef_ctx* c = sc->ctx;
+  Dev d(c->device);
+  hipStream_t s = (hipStream_t)stream;
+  const double rows = (double)T * S;
+  HIP_TRY(prof_launch(c, s, "score_step_kernel", rows * (14 * 4 + 4 + 24 + (rows_out ? 20 : 0)), rows * 60, [&] {
+    return launch_score_step(sc->log, track, quat, pos, status, quat_true, pos_true, T, S, rows_out, s);
+  }));
+  return SPEF_OK;
+}
+
+int spef_score_finalize(spef_score* sc, double* stats, void* stream) {
+  if (!sc || !stats) return fail(SPEF_ERR_ARG, "null argument");
+  spef_ctx* c = sc->ctx;
+  Dev d(c->device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(prof_launch(c, s, "score_finalize_kernel", 0.0, 0.0, [&] {
+    return launch_score_finalize(sc->log, sc->n_tracks, sc->scratch, sc->scratch_stride, stats, s);
+  }));
+  return SPEF_OK;
+}
+
+int spef_score_log(spef_score* sc, int track, int group, int first, int n, float* rows, int* flags, void* stream) {
+  if (!sc || !rows || !flags) return fail(SPEF_ERR_ARG, "null argument");
+  if (track < 0 || track >= sc->n_tracks) return fail(SPEF_ERR_ARG, "track index out of range");
+  if (group < 0 || group >= sc->log.n_groups) return fail(SPEF_ERR_ARG, "group index out of range");
+  if (first < 0 || n < 0 || (int64_t)first + n > sc->log.capacity) return fail(SPEF_ERR_ARG, "slots out of range");
+  Dev d(sc->device);
+  HIP_TRY(launch_score_read(sc->log, track, group, first, n, rows, flags, (hipStream_t)stream));
+  return SPEF_OK;
+}
+
 int spef_set_keypoints(spef_ctx* c, const float* kp3d, int n, const double* K, float nu, float nv) {
   if (!c || !kp3d || !K || n < 4 || n > 16) return fail(SPEF_ERR_ARG, "bad keypoint configuration");
   Dev d(c->device);

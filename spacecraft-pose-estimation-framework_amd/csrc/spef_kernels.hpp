@@ -184,6 +184,37 @@ hipError_t launch_video_set_state(const VideoHead& ori, const VideoHead& pos, fl
                                   int stream, const float* ori_pdf, const float* pos_pdf, const float* still_pole,
                                   const float* video_pole, hipStream_t s);
 
+// ---- pose scoring (k_score.hip; SPEUtils.get_score, src/spe/spe_utils.py:103-159, and the statistics of
+// src/tools/evaluation.py:59-99) ----
+// Rows are time-major: row t * S + s belongs to group s. The logs of all (track, group) pairs:
+struct ScoreLog {
+  float* rows;         // [n_tracks][n_groups][capacity][5]: pos_err, pos_norm, ori_rad, ori_deg, ori_stable
+  int* flags;          // [n_tracks][n_groups][capacity]: 1 dot > 1.01, 2 non-finite input, 4 zero target, 8 status
+  int* count;          // [n_tracks][n_groups] rows logged (<= capacity)
+  long long* dropped;  // [n_tracks][n_groups] rows that arrived after the log was full
+  int n_groups, capacity;
+};
+constexpr unsigned SCORE_TILE = 8192;   // rows the finalize kernel sorts in LDS (32 KiB); spef_amd.score.LDS_ROWS
+enum ScoreField : int {                 // spef_score_field (include/spef.h), spef_amd.score.STAT_FIELDS
+  SF_N = 0, SF_N_BAD, SF_N_DROPPED, SF_ORI_SCORE, SF_POS_SCORE, SF_ESA_SCORE, SF_ORI_ERROR, SF_POS_ERROR, SF_ORI_STD,
+  SF_POS_STD, SF_ORI_MEDIAN, SF_POS_MEDIAN, SF_ORI_MAD, SF_POS_MAD, SF_ORI_MIN, SF_ORI_MAX, SF_POS_MIN, SF_POS_MAX,
+  SF_FLAGS, SCORE_FIELDS
+};
+// Score T * S rows into the logs of `track` (and rows_out [T * S][5] when not null), then advance the counts by T:
+// two kernels, no host value. status (nullable): the rows' decode status.
+hipError_t launch_score_step(const ScoreLog& lg, int track, const float* quat, const float* pos, const int* status,
+                             const float* quat_true, const float* pos_true, int T, int S, float* rows_out,
+                             hipStream_t s);
+// Clear the counts of `group` in every track (all groups: -1).
+hipError_t launch_score_reset(const ScoreLog& lg, int n_tracks, int group, hipStream_t s);
+// stats [n_groups][n_tracks][SCORE_FIELDS] doubles. scratch: 2 * n_groups * n_tracks regions of scratch_stride floats
+// (the capacity rounded up to a power of two), needed when the capacity exceeds SCORE_TILE.
+hipError_t launch_score_finalize(const ScoreLog& lg, int n_tracks, float* scratch, unsigned scratch_stride,
+                                 double* stats, hipStream_t s);
+// Copy n log slots from `first` of (track, group) to rows [n][5] / flags [n].
+hipError_t launch_score_read(const ScoreLog& lg, int track, int group, int first, int n, float* rows, int* flags,
+                             hipStream_t s);
+
 // ---- INT8 path (k_q8.hip; integer semantics of oracle/int8_ref.py) ----
 enum QEpi : int { QEPI_RELU = 0, QEPI_PROJ = 1, QEPI_PROJ_RES = 2, QEPI_FC = 3 };
 

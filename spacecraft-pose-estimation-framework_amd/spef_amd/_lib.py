@@ -42,6 +42,12 @@ SIGNATURES = {
     'spef_video_set_state': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     'spef_video_step': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'spef_video_destroy': (_i, [_vp]),
+    'spef_score_create': (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    'spef_score_reset': (_i, [_vp, _i, _vp]),
+    'spef_score_step': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    'spef_score_finalize': (_i, [_vp, _vp, _vp]),
+    'spef_score_log': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'spef_score_destroy': (_i, [_vp]),
     'spef_validate_blob': (_i, [_vp, _sz, _ip, _ip, _ip, _ip]),
     'spef_comm_unique_id': (_i, [_vp, _sz]),
     'spef_comm_init': (_i, [_i, _i, _i, _vp, _i, C.POINTER(_vp)]),

@@ -100,6 +100,102 @@ class VideoFilter:
             pass
 
 
+class PoseScorer:
+    """Device-side pose scoring and evaluation statistics (``Engine.scorer``; csrc/k_score.hip, the arithmetic is
+    stated in ``spef_amd.score``): one log of ``capacity`` rows per (group, track).
+
+    Rows are time-major like the video path's: a batch of ``T * n_groups`` rows holds T rows of every group, row
+    ``t * n_groups + g`` belongs to group g. ``step`` only enqueues kernels on the current stream (no allocation in
+    the library, no host sync): it can follow ``Engine.decode`` / ``VideoFilter.step`` and be captured in a HIP graph.
+    ``result`` is the one place that synchronises."""
+
+    def __init__(self, engine: 'Engine', n_groups: int = 1, n_tracks: int = 1, capacity: int = 1 << 16):
+        from . import score as SC
+        self.engine = engine
+        self.lib = engine.lib
+        self.device = engine.device
+        self.n_groups, self.n_tracks, self.capacity = int(n_groups), int(n_tracks), int(capacity)
+        self.fields = SC.STAT_FIELDS
+        h = C.c_void_p()
+        L.check(self.lib.spef_score_create(engine.ctx, self.n_groups, self.n_tracks, self.capacity, C.byref(h)))
+        self.handle = h
+        self.last_event = None   # StreamPipeline: the event after the last step it enqueued (steps serialise)
+
+    def _dev(self, a, width: int) -> torch.Tensor:
+        """A float32 [rows, width] device tensor of ``a`` (device tensors are used as they are; host arrays are
+        copied on the current stream, which then owns the copy)."""
+        if isinstance(a, torch.Tensor):
+            t = a if a.dtype == torch.float32 else a.float()
+        else:
+            t = torch.from_numpy(np.array(a, dtype=np.float32, order='C'))   # a copy: read-only arrays are welcome
+        return t.to(self.device, non_blocking=True).reshape(-1, width).contiguous()
+
+    def targets(self, targets):
+        """``targets`` ({'ori', 'pos'} or a (quat, pos) pair; tensors or arrays) -> the device pair ``step`` takes."""
+        q, p = (targets['ori'], targets['pos']) if isinstance(targets, dict) else targets
+        return self._dev(q, 4), self._dev(p, 3)
+
+    def step(self, track: int, dec, targets, T: Optional[int] = None, want_rows: bool = False):
+        """Score one batch into the logs of ``track``. ``dec``: a decode dict ('ori', 'pos' and, when present,
+        'status') or a (quat, pos) pair; ``targets``: as ``targets()``. ``T``: time steps in the batch (default
+        rows / n_groups). -> the rows [T * n_groups, 5] (``score.ROW_FIELDS``) as a device tensor when ``want_rows``."""
+        if isinstance(dec, dict):
+            quat, pos, status = dec['ori'], dec['pos'], dec.get('status')
+        else:
+            (quat, pos), status = dec, None
+        quat, pos = self._dev(quat, 4), self._dev(pos, 3)
+        qt, pt = self.targets(targets)
+        B, S = quat.shape[0], self.n_groups
+        if T is None:
+            T = B // S
+        assert pos.shape[0] == B and qt.shape[0] == B and pt.shape[0] == B, 'poses and targets differ in rows'
+        assert B == T * S, f'{B} rows are not T = {T} steps of {S} groups'
+        if status is not None:
+            assert status.device == self.device and status.dtype == torch.int32 and status.numel() == B
+            status = status.contiguous()
+        rows = torch.empty((B, 5), dtype=torch.float32, device=self.device) if want_rows else None
+        L.check(self.lib.spef_score_step(self.handle, int(track), _ptr(quat), _ptr(pos), _ptr(status), _ptr(qt),
+                                         _ptr(pt), T, S, _ptr(rows), _stream(self.device)))
+        return rows
+
+    def reset(self, group: Optional[int] = None) -> None:
+        """Empty the logs of one group (all groups: None); enqueued on the current stream."""
+        L.check(self.lib.spef_score_reset(self.handle, -1 if group is None else int(group), _stream(self.device)))
+
+    def result(self) -> dict:
+        """Run the statistics kernel and synchronise once -> {field: float64 array [n_groups, n_tracks]} for the
+        fields of ``score.STAT_FIELDS`` (with no good row every statistic is NaN)."""
+        cur = torch.cuda.current_stream(self.device)
+        if self.last_event is not None:
+            cur.wait_event(self.last_event)
+        stats = torch.empty((self.n_groups, self.n_tracks, len(self.fields)), dtype=torch.float64, device=self.device)
+        L.check(self.lib.spef_score_finalize(self.handle, _ptr(stats), _stream(self.device)))
+        host = stats.cpu().numpy()
+        return {k: host[:, :, i].copy() for i, k in enumerate(self.fields)}
+
+    def log(self, track: int = 0, group: int = 0, first: int = 0, n: Optional[int] = None):
+        """Slots [first, first + n) of one log -> (rows float32 [n, 5], flags int32 [n]) NumPy arrays
+        (synchronises). ``n`` defaults to the capacity's remainder; slots past the log's count hold stale data."""
+        n = self.capacity - first if n is None else int(n)
+        rows = torch.empty((n, 5), dtype=torch.float32, device=self.device)
+        flags = torch.empty((n,), dtype=torch.int32, device=self.device)
+        L.check(self.lib.spef_score_log(self.handle, int(track), int(group), int(first), n, _ptr(rows), _ptr(flags),
+                                        _stream(self.device)))
+        return rows.cpu().numpy(), flags.cpu().numpy()
+
+    def close(self) -> None:
+        if getattr(self, 'handle', None):
+            torch.cuda.synchronize(self.device)
+            self.lib.spef_score_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """Loaded weights + workspace on one GPU.
 
@@ -125,6 +221,7 @@ class Engine:
         self.epoch = 0
         self.head = self.n_out0 = self.n_out1 = self.n_ops = None
         self.dtype = None
+        self.blob = None
         if blob is not None:
             self.load(blob)
 
@@ -136,6 +233,7 @@ class Engine:
         else:
             buf = C.create_string_buffer(bytes(blob), len(blob))
             L.check(self.lib.spef_load_weights(self.ctx, buf, len(blob)))
+        self.blob = blob   # kept so that further contexts (evaluation_device's StreamPipeline) load the same weights
         self._model_info()
 
     def bcast_weights(self, comm, root: int = 0) -> None:
@@ -246,6 +344,12 @@ class Engine:
         streams on this engine's device; the defaults are the reference ``Inference`` engine's (inference.py:38-39).
         Needs both decode tables."""
         return VideoFilter(self, n_streams, metric, n_ori, alpha_ori, n_pos, alpha_pos)
+
+    def scorer(self, n_groups: int = 1, n_tracks: int = 1, capacity: int = 1 << 16) -> 'PoseScorer':
+        """Device-side scoring (``SPEUtils.get_score``) and evaluation statistics for ``n_groups`` groups of rows
+        (videos, cameras; 1 for a plain evaluation) and ``n_tracks`` kinds of pose (still, filtered), with room for
+        ``capacity`` rows per (group, track), at most 2^20."""
+        return PoseScorer(self, n_groups, n_tracks, capacity)
 
     def set_fused(self, on: bool) -> None:
         """Fused inverted-residual blocks (default) or one kernel per conv (reference schedule)."""

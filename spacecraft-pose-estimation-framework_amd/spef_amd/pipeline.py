@@ -62,7 +62,7 @@ class StreamPipeline:
             e.reserve(B, H, W)
 
     def submit(self, frames: torch.Tensor, ori_mode: int = L.CLASSIFICATION, pos_mode: int = L.REGRESSION,
-               want_soft: bool = True, video=None) -> dict:
+               want_soft: bool = True, video=None, score=None) -> dict:
         """Enqueue forward + decode of one batch on the next stream; returns the decode dict (device tensors,
         valid once that stream reaches them -- ``synchronize()`` or the dict's 'event').
 
@@ -70,7 +70,13 @@ class StreamPipeline:
         n_streams frames, classification heads, ``want_soft``). Its step is enqueued on the slot's stream after the
         decode -- outside the slot's recorded graph -- and ordered after the previous submit's step by an event:
         the forwards of the slots still overlap, only the filter steps serialise. The filtered result is the
-        dict's 'video' entry (``VideoFilter.step``), and 'event' then covers it too."""
+        dict's 'video' entry (``VideoFilter.step``), and 'event' then covers it too.
+
+        ``score``: ``(scorer, targets)`` -- a ``PoseScorer`` (``Engine.scorer``) whose groups this batch holds,
+        time-major, and the batch's true poses ({'ori', 'pos'}; device tensors, or host arrays that are copied).
+        The scoring step is enqueued on the slot's stream after the decode (and after the video step: track 0 then
+        logs the still poses, track 1 the filtered ones), outside the recorded graph, and ordered after the previous
+        submit's scoring step by an event exactly as the video steps are."""
         i = self._next
         self._next = (i + 1) % self.depth
         eng, s = self.engines[i], self.streams[i]
@@ -105,7 +111,24 @@ class StreamPipeline:
                 ev = torch.cuda.Event()
                 ev.record(s)
             video.last_event = dec['event'] = ev
+        if score is not None:
+            self._score(s, dec, score, dec.get('video'))
         return dec
+
+    def _score(self, s, dec: dict, score, video_dec=None) -> None:
+        scorer, targets = score
+        B = dec['ori'].shape[0]
+        assert B % scorer.n_groups == 0, f'{B} rows are not whole time steps of {scorer.n_groups} groups'
+        with torch.cuda.stream(s):
+            tg = scorer.targets(targets)                 # host targets: copied before the wait below
+            if scorer.last_event is not None:
+                s.wait_event(scorer.last_event)          # the logs' counts: steps in submit order
+            scorer.step(0, dec, tg, B // scorer.n_groups)
+            if video_dec is not None:
+                scorer.step(1, video_dec, tg, B // scorer.n_groups)
+            ev = torch.cuda.Event()
+            ev.record(s)
+        scorer.last_event = dec['event'] = ev
 
     def _drop_graphs(self, i: int) -> None:
         for k in [k for k in self._graphs if k[0] == i]:
@@ -146,9 +169,10 @@ class StreamPipeline:
         for e in self.engines:
             e.set_keypoints(kp3d, K, nu, nv, dist)
 
-    def submit_keypoints(self, frames: torch.Tensor) -> dict:
+    def submit_keypoints(self, frames: torch.Tensor, score=None) -> dict:
         """Keypoint mode: forward (KeypointRegressionHead) + sigmoid + batched EPnP of one batch on the next stream;
-        returns the decode dict of Engine.decode_keypoints plus 'raw' and 'event' (as submit())."""
+        returns the decode dict of Engine.decode_keypoints plus 'raw' and 'event' (as submit()). ``score``: as in
+        ``submit``."""
         i = self._next
         self._next = (i + 1) % self.depth
         eng, s = self.engines[i], self.streams[i]
@@ -161,6 +185,8 @@ class StreamPipeline:
             ev.record(s)
         dec['raw'] = raw
         dec['event'] = ev
+        if score is not None:
+            self._score(s, dec, score)
         return dec
 
     def synchronize(self) -> None:

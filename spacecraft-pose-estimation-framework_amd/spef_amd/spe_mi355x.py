@@ -41,6 +41,7 @@ class SPEMi355x:
         self.device = torch.device(device)
         self.engine = None
         self._video = None          # (configuration, VideoFilter) of predict_video
+        self._pipe = None           # StreamPipeline of evaluation_device
         self.update_model(model, self.device)
 
     # ------------------------------------------------------------------ lifecycle (spe_torch.py:78-124)
@@ -83,6 +84,7 @@ class SPEMi355x:
 
     def delete_model(self) -> None:
         self._close_video()
+        self._close_pipe()
         if self.engine is not None:
             self.engine.close()
         self.engine = None
@@ -143,14 +145,38 @@ class SPEMi355x:
             self._video[1].close()
         self._video = None
 
-    def predict_video(self, images: torch.Tensor, n_streams: int = 1, metric: str = 'l2',
+    def eval_pipeline(self, depth: int = 3):
+        """A ``StreamPipeline`` of ``depth`` further contexts holding this model's weights and decode configuration
+        (``evaluation_device`` drives it); created on first use, closed with the model."""
+        from .pipeline import StreamPipeline
+        if self._pipe is None or self._pipe.depth != depth:
+            self._close_pipe()
+            if self.engine.blob is None:
+                raise AssertionError('the engine does not hold its weight blob (weights received by broadcast)')
+            tables = self.engine._decode_tables or (None, None)
+            self._pipe = StreamPipeline(self.engine.blob, self.device, depth, *tables)
+            if self.keypoint_mode:
+                kp, kk, dd = self.engine._kp
+                cam = self.spe_utils.keypoints.camera
+                self._pipe.set_keypoints(kp, kk.reshape(3, 3), float(cam.nu), float(cam.nv), dd if dd.size else None)
+        return self._pipe
+
+    def _close_pipe(self) -> None:
+        if getattr(self, '_pipe', None) is not None:
+            self._pipe.close()
+        self._pipe = None
+
+    def predict_video(self, images: torch.Tensor, n_streams: int = 1, metric: str = 'l2', targets=None, scorer=None,
                       **params) -> Tuple[Dict, Dict, float]:
         """Time-major video frames ``images`` [T * n_streams, 3, H, W] (row t * n_streams + s = step t of stream
         s) -> (still pose, video pose, latency ms): one batched forward, one decode and one video-filter step, all
         on the GPU. Both are batched NumPy dicts with the keys of ``Inference.predict``: the still pose has 'ori',
         'pos', 'ori_soft', 'pos_soft'; the video pose adds 'ori_distance' / 'pos_distance' and holds the filtered
         PDFs and their decode. The quaternions of both follow their stream's pole (inference.py:136-144). The
-        filter's state persists between calls (``video_filter(...).reset()`` starts new videos)."""
+        filter's state persists between calls (``video_filter(...).reset()`` starts new videos).
+        With ``targets`` ({'ori', 'pos'} of the frames) and ``scorer`` (``engine.scorer(n_streams, 2, capacity)``)
+        both poses are scored on the device as well: track 0 logs the still poses and track 1 the filtered ones, one
+        group per stream; ``scorer.result()`` then gives the still against filtered statistics per video."""
         if self.engine is None:
             raise AssertionError('no model loaded')
         if self.ori_mode != L.CLASSIFICATION or self.pos_mode != L.CLASSIFICATION:
@@ -165,6 +191,12 @@ class SPEMi355x:
         start.record()
         _, _, dec = self._run(x)
         vid = vf.step(dec, B // n_streams)
+        if targets is not None and scorer is not None:
+            if scorer.n_groups != n_streams or scorer.n_tracks < 2:
+                raise AssertionError(f'the scorer needs {n_streams} groups and 2 tracks')
+            tg = scorer.targets(targets)
+            scorer.step(0, dec, tg, B // n_streams)
+            scorer.step(1, vid, tg, B // n_streams)
         end.record()
         end.synchronize()
         still = self._pose(dec)

@@ -21,13 +21,15 @@ def main(argv=None):
     ap.add_argument('--data', help='SPEED dataset root (images/, valid.json, real.json)')
     ap.add_argument('--synthetic', type=int, default=2, help='synthetic batches when --data is absent')
     ap.add_argument('--num-predict', type=int)
+    ap.add_argument('--device-eval', action='store_true',
+                    help='score on the device (evaluation_device) instead of the per-batch host loop')
     a = ap.parse_args(argv)
     import torch
     from ..config import load_config, to_spe_utils
     from ..data.synthetic import speed_like_loader
     from ..spe.camera import CAMERAS
     from ..spe_mi355x import SPEMi355x
-    from .evaluation import evaluation
+    from .evaluation import evaluation, evaluation_device
 
     cfg = load_config(os.path.join(a.build, 'config.yaml'))
     dev = torch.device(f'cuda:{cfg.MI355X.DEVICE}')
@@ -52,7 +54,10 @@ def main(argv=None):
     else:
         loaders = {'synthetic': speed_like_loader(a.synthetic, B, size)}
         splits = ('synthetic',)
-    score, error = evaluation(spe, loaders, su, splits)
+    if a.device_eval:   # scoring and statistics on the device, batches pipelined over three streams
+        score, error = evaluation_device(spe, loaders, su, splits)
+    else:
+        score, error = evaluation(spe, loaders, su, splits)
 
     img, _ = next(iter(speed_like_loader(1, B, size)))
     n = a.num_predict or cfg.MI355X.NUM_PREDICT

@@ -55,3 +55,53 @@ def evaluation(spe_model: Any, dataloader: Dict[str, Iterable], spe_utils,
         rec_error[phase]['ori_mad'].append(mad(error['ori']))
         rec_error[phase]['pos_mad'].append(mad(error['pos']))
     return rec_score, rec_error
+
+
+def evaluation_device(spe_model: Any, dataloader: Dict[str, Iterable], spe_utils,
+                      split: Tuple[str, ...] = ('test', 'valid'), capacity: int = 0):
+    """``evaluation()`` with the scoring on the device: the batches go through a depth-3 ``StreamPipeline`` of the
+    model's weights (``SPEMi355x.eval_pipeline``), each followed on its stream by a scoring step against its targets
+    (``PoseScorer``, csrc/k_score.hip); nothing is copied back and nothing synchronises per batch. One ``result()``
+    per phase yields the same records. The means are those of all images (``evaluation()`` weights its per-batch means
+    by the batch size: the same number up to rounding); std and MAD are taken over the float32 per-image errors.
+
+    Raises the reference's ValueError (spe_utils.py:137) at the end of a phase if a row's |q . q_true| exceeded 1.01,
+    and the decode's ValueError if a row's decode status was nonzero. ``capacity``: rows per phase (default: the
+    phase's dataset size when the loader tells it, else 2^20)."""
+    from ..score import FLAG_DOT, FLAG_STATUS
+    rec_score = {x: {'ori': [], 'pos': [], 'esa': []} for x in split}
+    rec_error = {x: {'ori': [], 'pos': [], 'ori_std': [], 'pos_std': [], 'ori_mad': [], 'pos_mad': []} for x in split}
+    pipe = spe_model.eval_pipeline(3)
+    dev = spe_model.device
+    for phase in split:
+        loader = dataloader[phase]
+        cap = capacity
+        if cap <= 0:
+            ds = getattr(loader, 'dataset', None)
+            cap = len(ds) if ds is not None and hasattr(ds, '__len__') else (1 << 20)
+        scorer = pipe.engine.scorer(1, 1, max(1, min(cap, 1 << 20)))
+        try:
+            for images, targets in loader:
+                x = images['torch'].to(dev, non_blocking=True).contiguous()
+                if spe_model.keypoint_mode:
+                    pipe.submit_keypoints(x, score=(scorer, targets))
+                else:
+                    pipe.submit(x, spe_model.ori_mode, spe_model.pos_mode, want_soft=False, score=(scorer, targets))
+            res = {k: float(v[0, 0]) for k, v in scorer.result().items()}
+        finally:
+            scorer.close()
+        flags = int(res['flags'])
+        if flags & FLAG_DOT:
+            raise ValueError('Intermediate sum issue due to error in model prediction (orientation)')
+        if flags & FLAG_STATUS:
+            raise ValueError('Error during pose decoding (a row of the phase has a nonzero decode status)')
+        if res['n_dropped']:
+            raise ValueError(f'{int(res["n_dropped"])} images of phase {phase!r} exceeded the scorer capacity {cap}')
+        rec_score[phase]['ori'].append(res['ori_score'])
+        rec_score[phase]['pos'].append(res['pos_score'])
+        rec_score[phase]['esa'].append(res['esa_score'])
+        for k in ('ori', 'pos'):
+            rec_error[phase][k].append(res[f'{k}_error'])
+            rec_error[phase][f'{k}_std'].append(res[f'{k}_std'])
+            rec_error[phase][f'{k}_mad'].append(res[f'{k}_mad'])
+    return rec_score, rec_error
