@@ -222,6 +222,40 @@ int spef_score_finalize(spef_score* score, double* stats, void* stream);
 int spef_score_log(spef_score* score, int track, int group, int first, int n, float* rows, int* flags, void* stream);
 int spef_score_destroy(spef_score* score);
 
+/* Histogram observers for the INT8 calibration: the statistic of every activation-quantizer input of the float model,
+ * accumulated on the device over as many frames as the caller streams (Calibration path;
+ * spef_amd.quant.observe_host is the NumPy twin and scales_from_stats turns the counts into scales).
+ *
+ * Statistic of a float32 value x with b = bits(|x|) as uint32: b >= 0x7f800000 (non-finite) counts in n_nonfinite and
+ * nowhere else; b < 103 << 23 (|x| < 2^-24: zeros, -0, denormals) in n_under; b >= 135 << 23 (|x| >= 2^8) in n_over;
+ * otherwise in bin k = (b - (103 << 23)) >> 15 of 8192 (32 binades x 256 sub-bins; the upper edge of bin k is the float
+ * with bits ((k + 1) << 15) + (103 << 23)). max_bits = max of b over the finite values. Every count is an exact
+ * uint64 and depends neither on launch geometry nor on how the frames are cut into calls.
+ *
+ * Taps (one per quantizer, in spef_amd.quant's QParams order; n_blocks inverted residuals in the loaded model):
+ *   0 image, 1 stem, 2 + 3 (i - 1) + {0, 1, 2} = quant / expand / dw of block i (1-based), 2 + 3 n_blocks final,
+ *   3 + 3 n_blocks last. quant of block i >= 2 sees the block input and, for a residual block, the project output
+ *   before the add; expand is absent when t == 1; taps that do not exist stay empty.
+ *
+ * spef_observer_create: taps from the model loaded in ctx; allocates all state (zeroed).
+ * spef_observe: the fp32 schedule (one kernel per conv) with the observer enqueued after every launch; features (or
+ *   NULL) receives what spef_backbone writes, bit-identical. SPEF_ERR_STATE unless the loaded blob is fp32 and
+ *   spef_reserve covers the size; SPEF_ERR_ARG for an observer created on a model with another op list. No allocation
+ *   and no host synchronisation: it can be stream-captured.
+ * spef_observer_update: feeds n float32 values of any device tensor (4-byte aligned) into a tap. SPEF_ERR_ARG for a
+ *   bad tap or n < 0; n == 0 is a no-op.
+ * spef_observer_read: copies the records of taps [first_tap, first_tap + n) to out_device, per tap 8 + n_bins uint64:
+ *   n_total, n_under, n_over, n_nonfinite, max_bits, 0, 0, 0, then the bins. Enqueued; no host synchronisation. */
+typedef struct spef_observer spef_observer;
+int spef_observer_create(spef_ctx* ctx, spef_observer** out);
+int spef_observer_info(const spef_observer* obs, int* n_taps, int* n_bins);
+int spef_observer_reset(spef_observer* obs, void* stream);
+int spef_observe(spef_ctx* ctx, spef_observer* obs, const void* input, int layout, int B, int H, int W,
+                 float* features, void* stream);
+int spef_observer_update(spef_observer* obs, int tap, const float* x, int64_t n, void* stream);
+int spef_observer_read(spef_observer* obs, int first_tap, int n, uint64_t* out_device, void* stream);
+int spef_observer_destroy(spef_observer* obs);
+
 /* Keypoint mode (ORI == POS == 'keypoints', config.py:53-58): the 3-D model points (host float32 n x 3,
  * e.g. tangoPoints.mat's 11 Tango keypoints, keypoints_utils.py:31-45), the camera matrix (host float64
  * 3x3 row-major) and the image size the keypoints are normalised by (Camera nu, nv; speed.py:18-32). */

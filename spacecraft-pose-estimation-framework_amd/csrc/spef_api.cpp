@@ -109,6 +109,17 @@ struct spef_ctx {
   size_t pool_next = 0;
 };
 
+// Histogram observers (k_observe.hip): one record of OBS_COUNTERS + OBS_BINS uint64 per tap of the loaded model.
+// Tap ids: 0 image, 1 stem, 2 + 3 (i - 1) + {0, 1, 2} = quant / expand / dw of block i (1-based), 2 + 3 n_blocks final,
+// 3 + 3 n_blocks last.
+struct spef_observer {
+  int device = 0;
+  int n_blocks = 0, n_taps = 0;
+  std::vector<std::array<uint32_t, 7>> geom;   // the op list the taps were laid out for
+  uint64_t* state = nullptr;
+  uint64_t* tap(int t) const { return state + (size_t)t * (OBS_COUNTERS + OBS_BINS); }
+};
+
 namespace {
 
 struct Dev {  // RAII device guard
@@ -252,8 +263,18 @@ int check_ready(spef_ctx* c, int B, int H, int W) {
 // Runs the backbone. mode: 0 = full (pool into c->pooled), 1 = stop after op `stop` and leave the
 // activation in *out_buf, 2 = unfused last conv (feature map in *out_buf).
 int run_backbone(spef_ctx* c, const void* input, int layout, int B, int H, int W, hipStream_t s, int mode,
-                 int stop, void** out_buf, int* oc, int* oh, int* ow, float* feat_f32 = nullptr) {
+                 int stop, void** out_buf, int* oc, int* oh, int* ow, float* feat_f32 = nullptr,
+                 const spef_observer* obs = nullptr) {
   const int dt = (int)c->hdr.dtype;
+  // obs (fp32 schedule only): after each launch the observer is enqueued on the buffer just written
+  // (spef_amd.quant.calibrate's taps; spef_observe)
+  const int obs_blocks = num_cus() * 5;   // 32 KiB of LDS each: five workgroups per CU
+  auto observe = [&](int tap, const void* p, int64_t n, bool u8 = false) -> hipError_t {
+    return prof_launch(c, s, u8 ? "observe_kernel<u8>" : "observe_kernel<f32>", (double)n * (u8 ? 1 : 4), 0.0, [&] {
+      return launch_observe(obs->tap(tap), p, n, u8, obs_blocks, s);
+    });
+  };
+  int blk = 0;   // 1-based index of the current inverted residual
   const bool f32 = dt == DT_F32;   // fp32 schedule: one kernel per conv (k_f32.hip), no fused kernels
   const bool x2 = dt == DT_X2 || dt == DT_MX;   // fp16x2 kernels: fused split-fp16 blocks (k_x2.hip)
   // fp16mx: the same weights; the block outputs with <= 24 channels (blocks 1-3: the 256^2 / 128^2 maps, DESIGN.md
@@ -334,16 +355,19 @@ int run_backbone(spef_ctx* c, const void* input, int layout, int B, int H, int W
       void* y = c->buf[0];
       const double px = (double)B * OH * OW;
       const double in_b = (double)B * h * w * 3 * (layout == IN_U8_NHWC ? 1 : 4);
+      if (obs) HIP_TRY(observe(0, input, (int64_t)B * h * w * 3, layout == IN_U8_NHWC));
       HIP_TRY(prof_launch(c, s, layout == IN_U8_NHWC ? "stem_kernel<u8>" : "stem_kernel<f32>",
                           in_b + px * 32 * es, px * 2 * 27 * 32, [&] {
         return launch_stem(x2 ? (int)DT_F32 : dt, layout, input, ptr<float>(c, op.w0), ptr<float>(c, op.b0), y, B, h,
                            w, OH, OW, s);
       }));
+      if (obs) HIP_TRY(observe(1, y, (int64_t)B * OH * OW * op.cout));
       cur = y;
       h = OH;
       w = OW;
       ch = (int)op.cout;
     } else if (op.kind == OP_IRB) {
+      ++blk;
       const int64_t M = (int64_t)B * h * w;
       const int OH = conv_out(h, (int)op.stride), OW = conv_out(w, (int)op.stride);
       const bool res = op.flags & 1u;
@@ -423,6 +447,8 @@ int run_backbone(spef_ctx* c, const void* input, int layout, int B, int H, int W
         w = OW;
         ch = (int)op.cout;
       } else {
+        const int tap0 = 2 + 3 * (blk - 1);   // quant, expand, dw of this block
+        if (obs && blk >= 2) HIP_TRY(observe(tap0, x, M * op.cin));
         void* h1 = x;
         if (expand) {
           h1 = pick({x});
@@ -431,6 +457,7 @@ int run_backbone(spef_ctx* c, const void* input, int layout, int B, int H, int W
             return pw_any(c, dt, EPI_RELU, x, ptr<void>(c, op.w0), ptr<float>(c, op.b0), nullptr, h1, M,
                              (int)op.cin, (int)op.hidden, s);
           }));
+          if (obs) HIP_TRY(observe(tap0 + 1, h1, M * op.hidden));
         }
         void* h2 = pick({x, h1});
         const double opx = (double)B * OH * OW;
@@ -444,17 +471,33 @@ int run_backbone(spef_ctx* c, const void* input, int layout, int B, int H, int W
         }));
         void* y = res ? pick({x, h2}) : pick({h2});
         const int64_t M2 = (int64_t)B * OH * OW;
-        HIP_TRY(prof_launch(c, s, pw_any_key(c, dt, res ? EPI_RES : EPI_NONE, op.cout),
-                            pw_bytes(M2, op.hidden, op.cout, res) * es / 2, 2.0 * M2 * op.hidden * op.cout, [&] {
-          return pw_any(c, dt, res ? EPI_RES : EPI_NONE, h2, ptr<void>(c, op.w2), ptr<float>(c, op.b2),
-                           res ? x : nullptr, y, M2, (int)op.hidden, (int)op.cout, s);
-        }));
+        if (obs) HIP_TRY(observe(tap0 + 2, h2, M2 * op.hidden));
+        if (obs && res) {
+          // the project output BEFORE the join goes into the block's shared quantizer as well: project without the
+          // residual, observe, then y += x -- the one fp32 add EPI_RES makes after the bias, so y is bit-identical
+          HIP_TRY(prof_launch(c, s, pw_any_key(c, dt, EPI_NONE, op.cout), pw_bytes(M2, op.hidden, op.cout, false) * es / 2,
+                              2.0 * M2 * op.hidden * op.cout, [&] {
+            return pw_any(c, dt, EPI_NONE, h2, ptr<void>(c, op.w2), ptr<float>(c, op.b2), nullptr, y, M2,
+                          (int)op.hidden, (int)op.cout, s);
+          }));
+          if (blk >= 2) HIP_TRY(observe(tap0, y, M2 * op.cout));
+          HIP_TRY(prof_launch(c, s, "add_f32_kernel", 3.0 * M2 * op.cout * 4, (double)M2 * op.cout, [&] {
+            return launch_add_f32((float*)y, (const float*)x, M2 * op.cout, s);
+          }));
+        } else {
+          HIP_TRY(prof_launch(c, s, pw_any_key(c, dt, res ? EPI_RES : EPI_NONE, op.cout),
+                              pw_bytes(M2, op.hidden, op.cout, res) * es / 2, 2.0 * M2 * op.hidden * op.cout, [&] {
+            return pw_any(c, dt, res ? EPI_RES : EPI_NONE, h2, ptr<void>(c, op.w2), ptr<float>(c, op.b2),
+                          res ? x : nullptr, y, M2, (int)op.hidden, (int)op.cout, s);
+          }));
+        }
         cur = y;
         h = OH;
         w = OW;
         ch = (int)op.cout;
       }
     } else if (op.kind == OP_LAST) {
+      if (obs) HIP_TRY(observe(2 + 3 * obs->n_blocks, cur, (int64_t)B * h * w * ch));
       if (x2 && mode == 0 && x2_pw_pool_supported(h * w, (int)op.cout)) {   // last conv + mean, map never stored
         float* part = (float*)pick({cur});
         const double M3 = (double)B * h * w;
@@ -525,6 +568,7 @@ int run_backbone(spef_ctx* c, const void* input, int layout, int B, int H, int W
         cur = y;
         ch = (int)op.cout;
       }
+      if (obs) HIP_TRY(observe(3 + 3 * obs->n_blocks, cur, (int64_t)B * h * w * ch));
       break;
     }
     if (mode == 1 && op_index == stop) break;
@@ -1637,6 +1681,96 @@ int spef_video_step(spef_ctx* c, spef_video* v, const float* ori_soft, const flo
     return launch_video_pole(quat, still_quat, v->poles, v->flags + 2 * (size_t)v->S, T, S, s);
   }));
   return SPEF_OK;
+}
+
+// ------------------------------------------------------------------------------------------ histogram observers
+static std::vector<std::array<uint32_t, 7>> op_geometry(const spef_ctx* c) {
+  std::vector<std::array<uint32_t, 7>> g;
+  for (const OpDesc& op : c->ops) g.push_back({op.kind, op.cin, op.cout, op.hidden, op.stride, op.expand, op.flags});
+  return g;
+}
+
+int spef_observer_destroy(spef_observer* o) {
+  if (!o) return SPEF_OK;
+  Dev d(o->device);
+  if (o->state) hipFree(o->state);
+  delete o;
+  return SPEF_OK;
+}
+
+int spef_observer_create(spef_ctx* c, spef_observer** out) {
+  if (!c || !out) return fail(SPEF_ERR_ARG, "null argument");
+  if (!c->loaded) return fail(SPEF_ERR_STATE, "weights not loaded (spef_load_weights)");
+  Dev d(c->device);
+  spef_observer* o = new spef_observer;
+  o->device = c->device;
+  o->geom = op_geometry(c);
+  for (const OpDesc& op : c->ops) o->n_blocks += (op.kind == OP_IRB || op.kind == OP_QIRB) ? 1 : 0;
+  o->n_taps = 4 + 3 * o->n_blocks;
+  const size_t bytes = (size_t)o->n_taps * (OBS_COUNTERS + OBS_BINS) * sizeof(uint64_t);
+  hipError_t e = hipMalloc(&o->state, bytes);
+  if (e == hipSuccess) e = hipMemset(o->state, 0, bytes);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    spef_observer_destroy(o);
+    return fail(SPEF_ERR_HIP, std::string("spef_observer_create: ") + hipGetErrorString(e));
+  }
+  *out = o;
+  return SPEF_OK;
+}
+
+int spef_observer_info(const spef_observer* o, int* n_taps, int* n_bins) {
+  if (!o) return fail(SPEF_ERR_ARG, "null observer");
+  if (n_taps) *n_taps = o->n_taps;
+  if (n_bins) *n_bins = OBS_BINS;
+  return SPEF_OK;
+}
+
+int spef_observer_reset(spef_observer* o, void* stream) {
+  if (!o) return fail(SPEF_ERR_ARG, "null observer");
+  Dev d(o->device);
+  HIP_TRY(launch_observe_reset(o->state, (int64_t)o->n_taps * (OBS_COUNTERS + OBS_BINS), (hipStream_t)stream));
+  return SPEF_OK;
+}
+
+int spef_observer_update(spef_observer* o, int tap, const float* x, int64_t n, void* stream) {
+  if (!o) return fail(SPEF_ERR_ARG, "null observer");
+  if (tap < 0 || tap >= o->n_taps) return fail(SPEF_ERR_ARG, "tap index out of range");
+  if (n < 0) return fail(SPEF_ERR_ARG, "negative element count");
+  if (n == 0) return SPEF_OK;
+  if (!x || ((uintptr_t)x & 3)) return fail(SPEF_ERR_ARG, "null or misaligned tensor");
+  Dev d(o->device);
+  HIP_TRY(launch_observe(o->tap(tap), x, n, false, num_cus() * 5, (hipStream_t)stream));
+  return SPEF_OK;
+}
+
+int spef_observer_read(spef_observer* o, int first_tap, int n, uint64_t* out_device, void* stream) {
+  if (!o || !out_device) return fail(SPEF_ERR_ARG, "null argument");
+  if (first_tap < 0 || n < 0 || (int64_t)first_tap + n > o->n_taps) return fail(SPEF_ERR_ARG, "taps out of range");
+  if (n == 0) return SPEF_OK;
+  Dev d(o->device);
+  HIP_TRY(hipMemcpyAsync(out_device, o->tap(first_tap), (size_t)n * (OBS_COUNTERS + OBS_BINS) * sizeof(uint64_t),
+                         hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return SPEF_OK;
+}
+
+int spef_observe(spef_ctx* c, spef_observer* o, const void* input, int layout, int B, int H, int W, float* features,
+                 void* stream) {
+  if (!c || !o) return fail(SPEF_ERR_ARG, "null argument");
+  if (!c->loaded) return fail(SPEF_ERR_STATE, "weights not loaded (spef_load_weights)");
+  if (c->hdr.dtype != DT_F32)
+    return fail(SPEF_ERR_STATE, "spef_observe needs an fp32 blob (the one-kernel-per-conv schedule)");
+  int rc = check_ready(c, B, H, W);
+  if (rc) return rc;
+  if (!input) return fail(SPEF_ERR_ARG, "null input");
+  if (layout != SPEF_IN_U8_NHWC && layout != SPEF_IN_F32_NCHW) return fail(SPEF_ERR_ARG, "bad layout");
+  if (layout == SPEF_IN_F32_NCHW && ((uintptr_t)input & 3)) return fail(SPEF_ERR_ARG, "misaligned float32 input");
+  if (o->device != c->device || o->geom != op_geometry(c))
+    return fail(SPEF_ERR_ARG, "the observer was created for a model with another op list");
+  Dev d(c->device);
+  void* feat = nullptr;
+  int fc_ = 0, fh = 0, fw = 0;
+  return run_backbone(c, input, layout, B, H, W, (hipStream_t)stream, 2, -1, &feat, &fc_, &fh, &fw, features, o);
 }
 
 // ------------------------------------------------------------------------------------------ pose scoring

@@ -215,6 +215,15 @@ hipError_t launch_score_finalize(const ScoreLog& lg, int n_tracks, float* scratc
 hipError_t launch_score_read(const ScoreLog& lg, int track, int group, int first, int n, float* rows, int* flags,
                              hipStream_t s);
 
+// ---- histogram observers of the INT8 calibration (k_observe.hip) ----
+constexpr int OBS_BINS = 8192, OBS_COUNTERS = 8;   // one tap's record: OBS_COUNTERS + OBS_BINS uint64
+// Add the statistic of n values at x (float32, 4-byte aligned; u8: uint8 pixels, value = u / 255) to the record `tap`,
+// on at most max_blocks workgroups per launch.
+hipError_t launch_observe(uint64_t* tap, const void* x, int64_t n, bool u8, int max_blocks, hipStream_t s);
+// y[i] += x[i], one fp32 add each.
+hipError_t launch_add_f32(float* y, const float* x, int64_t n, hipStream_t s);
+hipError_t launch_observe_reset(uint64_t* st, int64_t n_words, hipStream_t s);
+
 // ---- INT8 path (k_q8.hip; integer semantics of oracle/int8_ref.py) ----
 enum QEpi : int { QEPI_RELU = 0, QEPI_PROJ = 1, QEPI_PROJ_RES = 2, QEPI_FC = 3 };
 

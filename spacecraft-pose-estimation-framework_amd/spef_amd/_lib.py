@@ -48,6 +48,13 @@ SIGNATURES = {
     'spef_score_finalize': (_i, [_vp, _vp, _vp]),
     'spef_score_log': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'spef_score_destroy': (_i, [_vp]),
+    'spef_observer_create': (_i, [_vp, C.POINTER(_vp)]),
+    'spef_observer_info': (_i, [_vp, _ip, _ip]),
+    'spef_observer_reset': (_i, [_vp, _vp]),
+    'spef_observe': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'spef_observer_update': (_i, [_vp, _i, _vp, C.c_int64, _vp]),
+    'spef_observer_read': (_i, [_vp, _i, _i, _vp, _vp]),
+    'spef_observer_destroy': (_i, [_vp]),
     'spef_validate_blob': (_i, [_vp, _sz, _ip, _ip, _ip, _ip]),
     'spef_comm_unique_id': (_i, [_vp, _sz]),
     'spef_comm_init': (_i, [_i, _i, _i, _vp, _i, C.POINTER(_vp)]),

@@ -29,7 +29,10 @@ DEFAULTS: Dict[str, Any] = {
               'MILESTONES': (7, 20), 'GAMMA': 0.1, 'CLIP_BATCHNORM': False},
     # this target: weight storage / arithmetic type (fp16mx | fp16x2 | fp16 | bf16 | int8 | fp32), device, batch,
     # throughput loop length. fp16mx (the default) holds the north star's absolute bound at trained-scale heads.
-    'MI355X': {'DTYPE': 'fp16mx', 'DEVICE': 0, 'BATCH_SIZE': 64, 'NUM_PREDICT': 1000, 'CALIB_FRAMES': 16},
+    # int8 calibration: frame count, where it runs (host: quant.calibrate; device: quant.calibrate_device, histogram
+    # observers behind the fp32 schedule), clip method (percentile | mse | max; max on the device only) and percentile.
+    'MI355X': {'DTYPE': 'fp16mx', 'DEVICE': 0, 'BATCH_SIZE': 64, 'NUM_PREDICT': 1000, 'CALIB_FRAMES': 16,
+               'CALIB_ON_DEVICE': False, 'CALIB_METHOD': 'percentile', 'CALIB_PERCENTILE': 99.999},
 }
 
 
@@ -82,6 +85,7 @@ def load_config(path: str | None = None) -> Config:
         assert h['ORI'] == 'keypoints' and h['POS'] == 'keypoints', \
             "Both ORI and POS must be 'keypoints' if one is 'keypoints'"
     assert cfg['MI355X']['DTYPE'] in ('fp16mx', 'fp16', 'bf16', 'int8', 'fp32', 'fp16x2')
+    assert cfg['MI355X']['CALIB_METHOD'] in ('percentile', 'mse', 'max')
     return _wrap(cfg)
 
 

@@ -196,6 +196,69 @@ class PoseScorer:
             pass
 
 
+class ActivationObserver:
+    """Histogram observers behind every activation-quantizer input of the float model (``Engine.observer``;
+    csrc/k_observe.hip, the statistic is stated in ``spef_amd.quant.observe_host``): one record of 8 counters and
+    ``n_bins`` bins per tap, kept on the device and accumulated over every ``observe`` / ``update`` until ``reset``.
+
+    ``observe`` and ``update`` only enqueue kernels on the current stream (no allocation in the library, no host
+    sync) and can be captured in a HIP graph; ``read`` is the one place that synchronises."""
+
+    def __init__(self, engine: 'Engine'):
+        self.engine = engine
+        self.lib = engine.lib
+        self.device = engine.device
+        h = C.c_void_p()
+        L.check(self.lib.spef_observer_create(engine.ctx, C.byref(h)))
+        self.handle = h
+        nt, nb = C.c_int(), C.c_int()
+        L.check(self.lib.spef_observer_info(h, C.byref(nt), C.byref(nb)))
+        self.n_taps, self.n_bins = nt.value, nb.value
+
+    def observe(self, frames: torch.Tensor, features: Optional[torch.Tensor] = None) -> None:
+        """Run the fp32 schedule on ``frames`` (either layout of ``Engine.forward``) with every tap observed. The
+        engine must hold an fp32 blob. ``features`` (optional, the shape ``Engine.backbone`` returns) receives the
+        backbone output, bit-identical to ``Engine.backbone``'s."""
+        eng = self.engine
+        assert frames.device == self.device and frames.is_contiguous()
+        layout, B, H, W = eng._layout(frames)
+        eng.reserve(B, H, W)
+        if features is not None:
+            assert features.device == self.device and features.is_contiguous() and features.dtype == torch.float32
+        L.check(self.lib.spef_observe(eng.ctx, self.handle, _ptr(frames), layout, B, H, W, _ptr(features),
+                                      _stream(self.device)))
+
+    def update(self, tap: int, tensor: torch.Tensor) -> None:
+        """Add the values of a float32 device tensor to one tap."""
+        assert tensor.device == self.device and tensor.dtype == torch.float32 and tensor.is_contiguous()
+        L.check(self.lib.spef_observer_update(self.handle, int(tap), _ptr(tensor), tensor.numel(),
+                                              _stream(self.device)))
+
+    def reset(self) -> None:
+        """Zero every record; enqueued on the current stream."""
+        L.check(self.lib.spef_observer_reset(self.handle, _stream(self.device)))
+
+    def read(self):
+        """-> (counters uint64 [taps, 8] = n_total, n_under, n_over, n_nonfinite, max_bits, 0, 0, 0; hist uint64
+        [taps, n_bins]) as NumPy arrays (synchronises)."""
+        rec = torch.empty((self.n_taps, 8 + self.n_bins), dtype=torch.int64, device=self.device)
+        L.check(self.lib.spef_observer_read(self.handle, 0, self.n_taps, _ptr(rec), _stream(self.device)))
+        host = rec.cpu().numpy().view(np.uint64)
+        return host[:, :8].copy(), host[:, 8:].copy()
+
+    def close(self) -> None:
+        if getattr(self, 'handle', None):
+            torch.cuda.synchronize(self.device)
+            self.lib.spef_observer_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """Loaded weights + workspace on one GPU.
 
@@ -350,6 +413,11 @@ class Engine:
         (videos, cameras; 1 for a plain evaluation) and ``n_tracks`` kinds of pose (still, filtered), with room for
         ``capacity`` rows per (group, track), at most 2^20."""
         return PoseScorer(self, n_groups, n_tracks, capacity)
+
+    def observer(self) -> 'ActivationObserver':
+        """Histogram observers for the INT8 calibration (``quant.calibrate_device``): one tap per activation
+        quantizer of the loaded model. ``observe`` needs an fp32 blob in this engine."""
+        return ActivationObserver(self)
 
     def set_fused(self, on: bool) -> None:
         """Fused inverted-residual blocks (default) or one kernel per conv (reference schedule)."""

@@ -150,56 +150,251 @@ def _mse_clip(v: np.ndarray, levels: int, signed: bool) -> float:
     return float(best_c)
 
 
+def tap_ids(n_blocks: int = N_BLOCKS) -> Dict[str, int]:
+    """Quantizer name -> observer tap id (include/spef.h): 0 image, 1 stem, 2 + 3 (i - 1) + {0, 1, 2} = quant /
+    expand / dw of block i (1-based), then final and last."""
+    ids = {'image': 0, 'stem': 1, 'final': 2 + 3 * n_blocks, 'last': 3 + 3 * n_blocks}
+    for i in range(1, n_blocks + 1):
+        for k, part in enumerate(('quant', 'expand', 'dw')):
+            ids[f'blocks.{i}.{part}'] = 2 + 3 * (i - 1) + k
+    return ids
+
+
+def _quantizer(bw: BitWidths, name: str) -> Tuple[int, bool]:
+    """-> (top code, signed) of the quantizer behind the tap ``name``."""
+    if name == 'image':
+        return int_levels(bw.image), True
+    if name == 'stem':
+        return uint_levels(bw.first_conv[1]), False
+    if name == 'final':
+        return int_levels(bw.shared_act), True
+    if name == 'last':
+        return uint_levels(bw.last_conv[1]), False
+    _, i, part = name.split('.')
+    if part == 'quant':
+        return int_levels(bw.shared_act), True
+    return uint_levels(bw.block(int(i) - 1)[1 if part == 'expand' else 3]), False
+
+
 @torch.no_grad()
-def calibrate(sd: Dict, frames_u8: np.ndarray, percentile: float = 99.999, residual: bool = True,
-              bw: Optional[BitWidths] = None, method: str = 'percentile') -> Dict:
-    """Activation scales from the float model's statistics on ``frames_u8`` (B x H x W x 3 uint8), one per
-    quantizer (per tensor, as Brevitas), over the top code of its bit width (``bw``, default all 8):
-    ``method='percentile'`` clips at the ``percentile`` of |x|; ``'mse'`` picks the clip that minimises the
-    quantisation MSE of the observed values (a common PTQ initialisation; QAT refines the scales further)."""
-    bw = bw or BitWidths()
-    assert method in ('percentile', 'mse')
-    rng = np.random.default_rng(0)
-
-    def amax(*ts, levels=255, signed=False):
-        v = torch.cat([t.flatten() for t in ts]).numpy().astype(np.float64)
-        if method == 'mse':
-            if v.size > 1 << 20:
-                v = rng.choice(v, 1 << 20, replace=False)
-            return _mse_clip(v, levels, signed)
-        return float(max(np.percentile(np.abs(v), percentile), 1e-8))
-
+def taps(sd: Dict, frames_u8: np.ndarray, residual: bool = True):
+    """The quantizer inputs of the float model on ``frames_u8`` (B x H x W x 3 uint8): yields ``(tap id, name,
+    [float32 tensors])`` per quantizer in the reference graph's order -- image, stem, then per block expand (t != 1),
+    dw and quant (blocks >= 2: the block input and, for a residual block, the project output before the add), final,
+    last. These are the tensors ``calibrate`` takes its statistics from and the device observers see (spef_observe)."""
+    ids = tap_ids()
     x = torch.from_numpy(frames_u8).permute(0, 3, 1, 2).float() / 255.0
-    qp: Dict = {'image': amax(x, levels=int_levels(bw.image), signed=True) / int_levels(bw.image), 'blocks': []}
+    yield ids['image'], 'image', [x]
     x = F.relu(_cbn(sd, f'{FP}.0', x, 2, 1))
-    qp['stem'] = amax(x, levels=uint_levels(bw.first_conv[1])) / uint_levels(bw.first_conv[1])
+    yield ids['stem'], 'stem', [x]
     cin, idx = 32, 1
     for t, c, n, s in IR_SETTINGS:
         for i in range(n):
             stride = s if i == 0 else 1
             res = stride == 1 and cin == c and residual
-            b: Dict[str, Optional[float]] = {'quant': None, 'expand': None}
             y, j = x, 0
             if t != 1:
                 y = F.relu(_cbn(sd, f'{FP}.{idx}.conv.0', y, 1, 1))
-                lv = uint_levels(bw.block(idx - 1)[1])
-                b['expand'] = amax(y, levels=lv) / lv
+                yield ids[f'blocks.{idx}.expand'], f'blocks.{idx}.expand', [y]
                 j = 1
             y = F.relu(_cbn(sd, f'{FP}.{idx}.conv.{j}', y, stride, y.shape[1]))
-            lv = uint_levels(bw.block(idx - 1)[3])
-            b['dw'] = amax(y, levels=lv) / lv
+            yield ids[f'blocks.{idx}.dw'], f'blocks.{idx}.dw', [y]
             y = _cbn(sd, f'{FP}.{idx}.conv.{j + 1}', y, 1, 1)
             if idx > 1:
-                lv = int_levels(bw.shared_act)
-                b['quant'] = (amax(x, y, levels=lv, signed=True) if res else amax(x, levels=lv, signed=True)) / lv
+                yield ids[f'blocks.{idx}.quant'], f'blocks.{idx}.quant', [x, y] if res else [x]
             x = x + y if res else y
-            qp['blocks'].append(b)
             cin, idx = c, idx + 1
-    qp['final'] = amax(x, levels=int_levels(bw.shared_act), signed=True) / int_levels(bw.shared_act)
+    yield ids['final'], 'final', [x]
     x = F.relu(_cbn(sd, f'{FP}.{idx}', x, 1, 1))
-    qp['last'] = amax(x, levels=uint_levels(bw.last_conv[1])) / uint_levels(bw.last_conv[1])
+    yield ids['last'], 'last', [x]
+
+
+def _qp_from_clips(clip, bw: BitWidths) -> Dict:
+    """``clip``: quantizer name -> clip value (missing: the quantizer does not exist) -> the ``qp`` dict."""
+    def scale(name):
+        return None if name not in clip else clip[name] / _quantizer(bw, name)[0]
+    qp: Dict = {'image': scale('image'), 'blocks': [], 'stem': scale('stem')}
+    for i in range(1, N_BLOCKS + 1):
+        qp['blocks'].append({'quant': scale(f'blocks.{i}.quant'), 'expand': scale(f'blocks.{i}.expand'),
+                             'dw': scale(f'blocks.{i}.dw')})
+    qp['final'] = scale('final')
+    qp['last'] = scale('last')
     qp['bits'] = bw
     return qp
+
+
+def calibrate(sd: Dict, frames_u8: np.ndarray, percentile: float = 99.999, residual: bool = True,
+              bw: Optional[BitWidths] = None, method: str = 'percentile') -> Dict:
+    """Activation scales from the float model's statistics on ``frames_u8`` (B x H x W x 3 uint8), one per
+    quantizer (per tensor, as Brevitas), over the top code of its bit width (``bw``, default all 8):
+    ``method='percentile'`` clips at the ``percentile`` of |x|; ``'mse'`` picks the clip that minimises the
+    quantisation MSE of the observed values (a common PTQ initialisation; QAT refines the scales further).
+    Runs on the host over the raw activations (``taps``); ``calibrate_device`` is the streamed device form."""
+    bw = bw or BitWidths()
+    assert method in ('percentile', 'mse')
+    rng = np.random.default_rng(0)
+    clip = {}
+    for _, name, ts in taps(sd, frames_u8, residual):
+        levels, signed = _quantizer(bw, name)
+        v = torch.cat([t.flatten() for t in ts]).numpy().astype(np.float64)
+        if method == 'mse':
+            if v.size > 1 << 20:
+                v = rng.choice(v, 1 << 20, replace=False)
+            clip[name] = _mse_clip(v, levels, signed)
+        else:
+            clip[name] = float(max(np.percentile(np.abs(v), percentile), 1e-8))
+    return _qp_from_clips(clip, bw)
+
+
+# ---------------------------------------------------------------------------------------------- histogram observers
+# The statistic the device observers keep (csrc/k_observe.hip, include/spef.h): a histogram of |x| keyed by the
+# float32 bit pattern b = bits(|x|), 32 binades x 256 sub-bins from 2^-24 up to 2^8, plus exact counters.
+OBS_BINS = 8192
+OBS_COUNTERS = 8
+N_TOTAL, N_UNDER, N_OVER, N_NONFINITE, MAX_BITS = range(5)   # the counters of a tap's record
+_OBS_LO = 103 << 23   # bits(2^-24)
+_OBS_HI = 135 << 23   # bits(2^8)
+
+
+def observe_host(tensors):
+    """The NumPy twin of the observer kernel: ``tensors`` (one float32 array / tensor or several) -> (counters
+    uint64 [8], hist uint64 [8192]). Non-finite values count in n_nonfinite only; |x| < 2^-24 (zeros, denormals) in
+    n_under; |x| >= 2^8 in n_over; everything else in bin ``(b - (103 << 23)) >> 15``; max_bits is the max of b over
+    the finite values."""
+    if isinstance(tensors, (np.ndarray, torch.Tensor)):
+        tensors = [tensors]
+    counters = np.zeros(OBS_COUNTERS, np.uint64)
+    hist = np.zeros(OBS_BINS, np.uint64)
+    for t in tensors:
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        assert a.dtype == np.float32, 'the observers see float32 values'
+        b = np.ascontiguousarray(a).reshape(-1).view(np.uint32) & np.uint32(0x7fffffff)
+        finite = b < np.uint32(0x7f800000)
+        fb = b[finite]
+        binned = fb[(fb >= _OBS_LO) & (fb < _OBS_HI)]
+        counters[N_TOTAL] += np.uint64(b.size)
+        counters[N_UNDER] += np.uint64(np.count_nonzero(fb < _OBS_LO))
+        counters[N_OVER] += np.uint64(np.count_nonzero(fb >= _OBS_HI))
+        counters[N_NONFINITE] += np.uint64(b.size - fb.size)
+        if fb.size:
+            counters[MAX_BITS] = max(counters[MAX_BITS], np.uint64(fb.max()))
+        hist += np.bincount((binned - np.uint32(_OBS_LO)) >> np.uint32(15), minlength=OBS_BINS).astype(np.uint64)
+    return counters, hist
+
+
+def bin_edges() -> np.ndarray:
+    """float32 [8193]: edge k is the lower edge of bin k and the (exclusive) upper edge of bin k - 1."""
+    return ((np.arange(OBS_BINS + 1, dtype=np.uint32) << np.uint32(15)) + np.uint32(_OBS_LO)).view(np.float32)
+
+
+def _bits_to_float(b) -> float:
+    return float(np.array([int(b)], np.uint32).view(np.float32)[0])
+
+
+def _hist_percentile(counters, hist, percentile: float) -> float:
+    """The upper edge of the bin holding the order statistic of rank ceil(p / 100 (n - 1)) of the finite |x|, capped
+    at the tap's max: at least the exact order statistic and at most (1 + 2^-8) times it. 0 when the rank falls in
+    the underflow, the max when it falls in the overflow."""
+    n_fin = int(counters[N_TOTAL]) - int(counters[N_NONFINITE])
+    if n_fin <= 0:
+        return 0.0
+    mx = _bits_to_float(counters[MAX_BITS])
+    r = int(np.ceil(percentile / 100.0 * (n_fin - 1)))
+    r -= int(counters[N_UNDER])
+    if r < 0:
+        return 0.0
+    cum = np.cumsum(hist.astype(np.uint64))
+    k = int(np.searchsorted(cum, np.uint64(r), side='right'))   # first bin whose cumulative count exceeds r
+    if k >= OBS_BINS:
+        return mx
+    return min(float(bin_edges()[k + 1]), mx)
+
+
+def _hist_mse_clip(counters, hist, levels: int) -> float:
+    """``_mse_clip`` over the histogram: the same grid of clips f max|x|, the error evaluated at the bin midpoints
+    (capped at the max) weighted by the counts, the underflow counted as 0 and the overflow as the max. The histogram
+    holds |x|, so a signed quantizer is searched over its positive codes [0, levels]."""
+    n_fin = int(counters[N_TOTAL]) - int(counters[N_NONFINITE])
+    a = _bits_to_float(counters[MAX_BITS])
+    if n_fin <= 0 or a <= 0:
+        return 1e-8
+    e = bin_edges().astype(np.float64)
+    nz = np.nonzero(hist)[0]
+    v = np.minimum(0.5 * (e[nz] + e[nz + 1]), a)
+    w = hist[nz].astype(np.float64)
+    if int(counters[N_OVER]):
+        v, w = np.append(v, a), np.append(w, float(counters[N_OVER]))
+    best, best_c = np.inf, a
+    for f in np.linspace(0.05, 1.0, 96):
+        sc = f * a / levels
+        err = float(np.sum(w * (np.clip(np.rint(v / sc), 0, levels) * sc - v) ** 2)) / n_fin
+        if err < best:
+            best, best_c = err, f * a
+    return float(best_c)
+
+
+def scales_from_stats(counters: np.ndarray, hist: np.ndarray, bw: Optional[BitWidths] = None,
+                      method: str = 'percentile', percentile: float = 99.999, residual: bool = True) -> Dict:
+    """Observer statistics (``counters`` [taps x 8], ``hist`` [taps x 8192]: ``ActivationObserver.read`` or
+    ``observe_host`` per tap) -> the ``qp`` dict ``calibrate`` returns. Host fp64 over the integer counts.
+    ``method``: 'max' (the tap's max), 'percentile' (``_hist_percentile``, floored at 1e-8) or 'mse'
+    (``_hist_mse_clip``)."""
+    bw = bw or BitWidths()
+    assert method in ('max', 'percentile', 'mse')
+    counters, hist = np.asarray(counters, np.uint64), np.asarray(hist, np.uint64)
+    ids = tap_ids()
+    assert counters.shape == (len(ids), OBS_COUNTERS) and hist.shape == (len(ids), OBS_BINS), 'one record per tap'
+    arch = mobilenet_v2(residual=residual)
+    clip = {}
+    for name, t in ids.items():
+        if '.' in name:
+            i, part = int(name.split('.')[1]), name.split('.')[2]
+            if (part == 'quant' and i == 1) or (part == 'expand' and arch.blocks[i - 1].expand == 1):
+                continue
+        c, h = counters[t], hist[t]
+        if method == 'max':
+            v = _bits_to_float(c[MAX_BITS])
+        elif method == 'percentile':
+            v = _hist_percentile(c, h, percentile)
+        else:
+            v = _hist_mse_clip(c, h, _quantizer(bw, name)[0])
+        clip[name] = float(max(v, 1e-8))
+    return _qp_from_clips(clip, bw)
+
+
+def calibrate_device(sd: Dict, frames, device=0, batch: int = 16, bw: Optional[BitWidths] = None,
+                     method: str = 'percentile', percentile: float = 99.999, residual: bool = True) -> Dict:
+    """``calibrate`` on the device: the exact fp32 schedule (one kernel per conv) runs over the frames with a
+    histogram observer behind every quantizer input, and the scales come from the integer counts
+    (``scales_from_stats``). ``frames``: a uint8 array [N x H x W x 3], cut into batches of ``batch``, or an iterable
+    of such batches (arrays or tensors of one frame size); they are streamed through the observers on a side stream
+    and the statistics are read once at the end, so any number of frames costs one record per quantizer."""
+    from . import blob as Bl
+    from .arch import arch_from_state_dict
+    from .engine import Engine
+    if not torch.cuda.is_available():
+        raise RuntimeError('calibrate_device needs a HIP device (quant.calibrate is the host path)')
+    dev = torch.device(device if not isinstance(device, int) else f'cuda:{device}')
+    if isinstance(frames, np.ndarray):
+        assert frames.dtype == np.uint8 and frames.ndim == 4 and frames.shape[3] == 3, 'N x H x W x 3 uint8 frames'
+        frames = [frames[i:i + batch] for i in range(0, frames.shape[0], batch)]   # views
+    eng = Engine(Bl.pack(sd, arch_from_state_dict(sd, residual=residual), dtype='fp32'), dev)
+    obs = None
+    try:
+        obs = eng.observer()
+        stream = torch.cuda.Stream(dev)
+        stream.wait_stream(torch.cuda.current_stream(dev))   # device batches made on the caller's stream
+        with torch.cuda.stream(stream):
+            for fr in frames:
+                x = fr if isinstance(fr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(fr))
+                x = x.to(dev, non_blocking=True).contiguous()
+                obs.observe(x)
+            counters, hist = obs.read()
+    finally:
+        if obs is not None:
+            obs.close()
+        eng.close()
+    return scales_from_stats(counters, hist, bw, method, percentile, residual)
 
 
 def validate(qp: Dict, residual: bool = True) -> None:

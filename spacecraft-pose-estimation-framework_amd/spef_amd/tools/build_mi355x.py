@@ -2,12 +2,19 @@
 
     python -m spef_amd.tools.build_mi355x --experiment experiments/train/<name> [--dtype fp16mx|fp16x2|fp16|bf16|int8|fp32]
         [--eval-variants fp32,fp16mx,fp16x2,fp16,bf16,int8 | none] [--eval-batches N]
+        [--calib host|device] [--calib-method percentile|mse|max] [--calib-frames N]
     python -m spef_amd.tools.build_mi355x --synthetic --out experiments/build/mi355x/synthetic
 
 Reads ``config.yaml`` + ``model/parameters.pt`` (+ ``model/bit_width.json`` for quantized models) of a
 reference training experiment (eval.py:20-27 layout; the checkpoint is loaded with ``weights_only=True``),
 folds BN and packs the weight blob (fp16/bf16, or int8 with activation scales calibrated on frames), and writes
 ``experiments/build/mi355x/<name>/{model.spef, config.yaml, build.json}``.
+
+int8 calibration (``MI355X.CALIB_*``): ``--calib host`` (the default) runs the float model in torch on the CPU over the
+raw activations (``quant.calibrate``); ``--calib device`` streams the frames through the fp32 schedule on the GPU
+with a histogram observer behind every quantizer (``quant.calibrate_device``: any number of frames, percentile, MSE
+or max clips as build_nvidia.py:86-127 offers) and is an error when no GPU is visible. ``build.json`` records where
+the calibration ran, the method, the frame count and the seconds.
 
 Then, like build_nvidia.py:331-343 / build_tvm.py:219-231 (every lowering variant evaluated on the host with the same
 ``evaluation()``), each precision variant of the experiment -- fp32 (the reference's arithmetic), fp16mx (the default:
@@ -36,14 +43,39 @@ import sys
 import time
 
 
-def pack_variant(sd, cfg, arch, dtype: str, calib_frames=None, bit_width=None):
+def calibrate_frames(sd, cfg, calib_frames, bit_width=None, info=None):
+    """The int8 activation scales on ``calib_frames``, on the host or on the device as ``cfg.MI355X.CALIB_*`` says.
+    ``info`` (a dict) receives where it ran, the method, the frame count and the seconds."""
+    from ..quant import calibrate, calibrate_device
+    m = cfg.MI355X
+    t0 = time.time()
+    if m.CALIB_ON_DEVICE:
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError('the calibration was asked to run on the device (--calib device / '
+                               'MI355X.CALIB_ON_DEVICE) and no GPU is visible; --calib host runs it on the CPU')
+        qp = calibrate_device(sd, calib_frames, device=m.DEVICE, batch=min(m.BATCH_SIZE, 64), bw=bit_width,
+                              method=m.CALIB_METHOD, percentile=m.CALIB_PERCENTILE,
+                              residual=cfg.MODEL.BACKBONE.RESIDUAL)
+    else:
+        if m.CALIB_METHOD == 'max':
+            raise ValueError("the host calibration offers 'percentile' and 'mse'; 'max' needs --calib device")
+        qp = calibrate(sd, calib_frames, percentile=m.CALIB_PERCENTILE, residual=cfg.MODEL.BACKBONE.RESIDUAL,
+                       bw=bit_width, method=m.CALIB_METHOD)
+    if info is not None:
+        info.update({'where': 'device' if m.CALIB_ON_DEVICE else 'host', 'method': m.CALIB_METHOD,
+                     'percentile': m.CALIB_PERCENTILE, 'frames': int(len(calib_frames)),
+                     'seconds': round(time.time() - t0, 3)})
+    return qp
+
+
+def pack_variant(sd, cfg, arch, dtype: str, calib_frames=None, bit_width=None, calib_info=None):
     """-> (blob bytes, int8 quantisation parameters or None)."""
     from .. import blob as Bl
     if dtype == 'int8':
         from ..blob_q8 import pack_int8
-        from ..quant import calibrate
         assert calib_frames is not None, 'int8 builds calibrate activation scales on frames'
-        qp = calibrate(sd, calib_frames, residual=cfg.MODEL.BACKBONE.RESIDUAL, bw=bit_width)
+        qp = calibrate_frames(sd, cfg, calib_frames, bit_width, calib_info)
         return pack_int8(sd, qp, arch), qp
     return Bl.pack(sd, arch, dtype=dtype), None
 
@@ -116,7 +148,8 @@ def build(sd, cfg, out_dir: str, dtype: str, calib_frames=None, bit_width=None) 
     os.makedirs(out_dir, exist_ok=True)
     arch = arch_from_state_dict(sd, residual=cfg.MODEL.BACKBONE.RESIDUAL)
     t0 = time.time()
-    blob, qp = pack_variant(sd, cfg, arch, dtype, calib_frames, bit_width)
+    calib_info = {}
+    blob, qp = pack_variant(sd, cfg, arch, dtype, calib_frames, bit_width, calib_info)
     if qp is not None:
         import dataclasses
         with open(os.path.join(out_dir, 'qparams.json'), 'w') as f:
@@ -128,6 +161,8 @@ def build(sd, cfg, out_dir: str, dtype: str, calib_frames=None, bit_width=None) 
     save_config(cfg, os.path.join(out_dir, 'config.yaml'))
     info = {'dtype': dtype, 'bytes': len(blob), 'sha256': hashlib.sha256(blob).hexdigest(), 'head': arch.head,
             'n_ori': arch.n_ori, 'n_pos': arch.n_pos, 'pack_seconds': round(time.time() - t0, 3)}
+    if qp is not None:
+        info['calibration'] = calib_info
     with open(os.path.join(out_dir, 'build.json'), 'w') as f:
         json.dump(info, f, indent=1)
     return info
@@ -146,6 +181,11 @@ def main(argv=None):
     ap.add_argument('--allow-out-of-bound', action='store_true',
                     help='keep the requested floating-point blob even when it misses the 1e-3 / 0.1 deg / 1 mm bound '
                          'against the fp32 variant (default: fall back to fp16x2, or fail)')
+    ap.add_argument('--calib', choices=['host', 'device'],
+                    help='int8: where the activation scales are calibrated (default: MI355X.CALIB_ON_DEVICE, host); '
+                         'device needs a GPU')
+    ap.add_argument('--calib-method', choices=['percentile', 'mse', 'max'], help='default: MI355X.CALIB_METHOD')
+    ap.add_argument('--calib-frames', type=int, help='default: MI355X.CALIB_FRAMES')
     ap.add_argument('--synthetic-head-std', type=float, default=None,
                     help='--synthetic: orientation Linear init std (default: the reference init, 0.01); 0.3 gives the '
                          'trained-scale heads of the reference-generated predict fixtures')
@@ -182,6 +222,14 @@ def main(argv=None):
     keypoints = cfg.MODEL.HEAD.ORI == 'keypoints'
     dtype = a.dtype or ('fp16x2' if keypoints and cfg.MI355X.DTYPE in ('fp16', 'fp16mx') else cfg.MI355X.DTYPE)
     out = a.out or os.path.join('experiments', 'build', 'mi355x', name)
+    if a.calib:
+        cfg.MI355X.CALIB_ON_DEVICE = a.calib == 'device'
+    if a.calib_method:
+        cfg.MI355X.CALIB_METHOD = a.calib_method
+    if a.calib_frames:
+        cfg.MI355X.CALIB_FRAMES = a.calib_frames
+    if dtype == 'int8' and cfg.MI355X.CALIB_ON_DEVICE and not torch.cuda.is_available():
+        ap.error('--calib device: no GPU is visible (--calib host calibrates on the CPU)')
     calib = synth_frames(cfg.MI355X.CALIB_FRAMES, *cfg.DATA.IMG_SIZE, 900)
     info = build(sd, cfg, out, dtype, calib if dtype == 'int8' else None, bit_width)
     rc = 0
