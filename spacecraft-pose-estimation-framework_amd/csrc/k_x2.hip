@@ -2403,8 +2403,165 @@ __global__ __launch_bounds__(NWV * 64) void x2_pws_kernel(const float* __restric
   }
 }
 
+// Wide form of the staged kernel (SPEF_OPT_TRIM bit 0; Kp = 320, Np % 320 == 0): 128 pixels x 320 output channels per
+// workgroup, each of the four waves 80 channels (5 tiles) x 128 pixels (8 tiles): 160 accumulator registers. A weight
+// fragment now serves 8 pixel tiles instead of 4 and a staged pixel block 320 channels instead of 256: per launch at
+// B = 64, 512^2 the workgroups read 210 MB of weights and 84 MB of activations from L2 (the 64 x 256 form: 420 + 105),
+// and the 512 workgroups are one full round at two per CU (1,280 were 2.5). The pixel block is staged in two K halves of
+// 160 (128 x 160 x (hi + lo) = 80 KB, the 64-pixel form's LDS size: still two workgroups per CU, 250-252 VGPRs with no
+// scratch at two waves per SIMD). Every accumulator tile sees the same three MFMAs per K step in the same K order from the same
+// bias, and each 64-pixel group's pool partial is the same sum (its four pixel tiles in order from 0.f, then the xor
+// shuffles), written to the same [M / 64][N] rows: bit-identical to the 64-pixel form. LDS rows of 160 halves (320 B:
+// rows four apart start on the same bank); the 16-B granule index is XOR-ed within its group of four by
+// (-(row / 4)) & 3, which makes the 16 lanes of every ds_read_b128 lane group (rows 0-3 and 12-15 of one k group, rows
+// 4-11 of its neighbour) cover the 64 banks once.
+struct X2PwsWide {
+  static constexpr int PT = 128, MT = PT / 16;   // pixels, pixel tiles per workgroup (and per wave)
+  static constexpr int NA = 5, NC = 4 * 16 * NA;   // channel tiles per wave, channels per workgroup
+  static constexpr int KP = 320, KH = KP / 2, GP = KH / 8;   // K, the staged K half, its 16-B granules per row
+  static constexpr int LDS_BYTES = PT * KH * 2 * (int)sizeof(_Float16);
+};
+template <bool POOL, typename T>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void x2_pws_kernel(const float* __restrict__ X, const _Float16* __restrict__ Wt, const float* __restrict__ bias,
+                   float* __restrict__ Y, int64_t M, int K, int N, int Np, int n_chunks, uint32_t nwg) {
+  constexpr int KP = T::KP, KH = T::KH, GP = T::GP, NA = T::NA, MT = T::MT;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  _Float16* Xh = reinterpret_cast<_Float16*>(smem);   // [128][KH] hi halves of the staged K half (swizzled granules)
+  _Float16* Xl = Xh + T::PT * KH;                      // [128][KH] lo halves
+  const uint32_t L = xcd_remap(blockIdx.x, nwg);
+  const int chunk = (int)(L % (uint32_t)n_chunks);
+  const int64_t m0 = (int64_t)(L / (uint32_t)n_chunks) * T::PT;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int r16 = lane & 15, kg = lane >> 4;
+  const int n0 = chunk * T::NC + wave * (16 * NA);
+  const _Float16* Wlo = Wt + (size_t)Np * KP;
+  f32x4 acc[NA][MT];
+#pragma unroll
+  for (int a = 0; a < NA; ++a) {
+    const float4 bb = *reinterpret_cast<const float4*>(bias + n0 + 16 * a + 4 * kg);
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[a][m] = f32x4{bb.x, bb.y, bb.z, bb.w};
+  }
+  f16x8 ah[NA], al[NA];
+  const _Float16* wrow = Wt + (size_t)(n0 + r16) * KP + 8 * kg;
+  auto load_a = [&](int k) {
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      ah[a] = *reinterpret_cast<const f16x8*>(wrow + 16 * a * KP + k);
+      al[a] = *reinterpret_cast<const f16x8*>(wrow + (Wlo - Wt) + 16 * a * KP + k);
+    }
+  };
+  const int boff = r16 * KH + 8 * (kg ^ ((0 - (r16 >> 2)) & 3));   // the lane's granule of pixel tile 0, K step 0
+#pragma unroll 1
+  for (int kb = 0; kb < KP; kb += KH) {
+    if (kb) __syncthreads();   // the first half's fragment reads done before the second overlays it
+    // ---- stage: thread (row tid / 4, granule tid % 4 + 4 j) of rows 0-63, then of rows 64-127: 8 fp32 -> hi / lo per
+    // piece, a row's five loads first (four lanes read one 128-B line; the two rows of an 8-lane ds_write_b128 group
+    // cover the 32 banks once)
+#pragma unroll 1
+    for (int h = 0; h < T::PT / 64; ++h) {
+      const int px = 64 * h + (tid >> 2), q = tid & 3;
+      const int64_t p = m0 + px;
+      const float* xp = X + (size_t)(p < M ? p : 0) * K + kb + 8 * q;
+      float4 v[GP / 4][2];
+#pragma unroll
+      for (int j = 0; j < GP / 4; ++j) {
+        v[j][0] = v[j][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (p < M && kb + 8 * q + 32 * j < K) {
+          v[j][0] = *reinterpret_cast<const float4*>(xp + 32 * j);
+          v[j][1] = *reinterpret_cast<const float4*>(xp + 32 * j + 4);
+        }
+      }
+      const int o = px * KH + 8 * (q ^ ((0 - (px >> 2)) & 3));
+#pragma unroll
+      for (int j = 0; j < GP / 4; ++j) {
+        const float f[8] = {v[j][0].x, v[j][0].y, v[j][0].z, v[j][0].w, v[j][1].x, v[j][1].y, v[j][1].z, v[j][1].w};
+        f16x8 hi, lo;
+        split8(f, hi, lo);
+        *reinterpret_cast<f16x8*>(Xh + o + 32 * j) = hi;
+        *reinterpret_cast<f16x8*>(Xl + o + 32 * j) = lo;
+      }
+    }
+    load_a(kb);
+    __syncthreads();
+#pragma unroll 1
+    for (int k0 = 0; k0 < KH; k0 += 32) {
+      f16x8 bh[2], bl[2];   // pixel tile m + 1's fragments are read while tile m's MFMAs run
+      bh[0] = *reinterpret_cast<const f16x8*>(Xh + boff + k0);
+      bl[0] = *reinterpret_cast<const f16x8*>(Xl + boff + k0);
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        if (m + 1 < MT) {
+          const int o = boff + 16 * (m + 1) * KH + k0;
+          bh[(m + 1) & 1] = *reinterpret_cast<const f16x8*>(Xh + o);
+          bl[(m + 1) & 1] = *reinterpret_cast<const f16x8*>(Xl + o);
+        }
+#pragma unroll
+        for (int a = 0; a < NA; ++a) acc[a][m] = mfma_x2(ah[a], al[a], bh[m & 1], bl[m & 1], acc[a][m]);
+      }
+      if (k0 + 32 < KH) load_a(kb + k0 + 32);
+    }
+  }
+  if constexpr (POOL) {   // two 64-pixel groups m0 + 64 h .. + 63, each all valid when it starts below M (M % 64 == 0)
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      const int i = n0 + 16 * a + 4 * kg;
+#pragma unroll
+      for (int h = 0; h < MT / 4; ++h) {
+        float sm[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float t = 0.f;
+#pragma unroll
+          for (int m = 4 * h; m < 4 * h + 4; ++m) t += fmaxf(acc[a][m][r], 0.f);
+#pragma unroll
+          for (int o = 1; o < 16; o <<= 1) t += __shfl_xor(t, o, 64);
+          sm[r] = t;
+        }
+        if (r16 == 0 && i < N && m0 + 64 * h < M)
+          *reinterpret_cast<float4*>(Y + (size_t)(m0 / 64 + h) * N + i) = make_float4(sm[0], sm[1], sm[2], sm[3]);
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int a = 0; a < NA; ++a) {
+    const int i = n0 + 16 * a + 4 * kg;
+    if (i >= N) continue;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int64_t p = m0 + 16 * m + r16;
+      if (p >= M) continue;
+      const f32x4 v = acc[a][m];
+      *reinterpret_cast<float4*>(Y + (size_t)p * N + i) =
+          make_float4(fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f));
+    }
+  }
+}
+
 static bool x2_pws_ok(int Kp, int Np) {
   return SPEF_X2_PWS && Kp % 64 == 0 && Kp <= 320 && Np % 256 == 0;   // (NWV 5 falls back to 4 unless Np % 320 == 0)
+}
+static bool x2_pws_wide_ok(int Kp, int Np) { return SPEF_X2_PWS && Kp == X2PwsWide::KP && Np % X2PwsWide::NC == 0; }
+
+template <bool POOL>
+static hipError_t x2_pws_wide_go(const void* x, const void* wt, const float* bias, float* y, int64_t M, int K, int N,
+                                 int Np, hipStream_t s) {
+  using T = X2PwsWide;
+  const int n_chunks = Np / T::NC;
+  const int64_t nwg64 = (M + T::PT - 1) / T::PT * n_chunks;
+  if (nwg64 > 0x7fffffff) return hipErrorInvalidValue;
+  const uint32_t nwg = (uint32_t)nwg64;
+  static DevOnce attr_set;
+  if (!attr_set.done()) {
+    hipError_t e = x2_set_lds(x2_pws_kernel<POOL, T>, T::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    attr_set.set();
+  }
+  x2_pws_kernel<POOL, T><<<nwg, 256, T::LDS_BYTES, s>>>((const float*)x, (const _Float16*)wt, bias, y, M, K, N, Np,
+                                                        n_chunks, nwg);
+  return hipGetLastError();
 }
 
 template <bool POOL>
@@ -2446,10 +2603,11 @@ __global__ __launch_bounds__(256) void x2_pool_reduce_kernel(const float* __rest
 }
 
 hipError_t launch_x2_pw_relu(const void* x, const void* wt, const float* bias, float* y, int64_t M, int K, int N,
-                             hipStream_t s) {
+                             hipStream_t s, bool wide) {
   if (M <= 0) return hipSuccess;
   const int Kp = (K + 31) & ~31, Np = (N + 15) & ~15;
   if ((K & 7) || (N & 3) || Np % 64) return hipErrorInvalidValue;
+  if (wide && x2_pws_wide_ok(Kp, Np)) return x2_pws_wide_go<false>(x, wt, bias, y, M, K, N, Np, s);
   if (x2_pws_ok(Kp, Np)) return x2_pws_go<false>(x, wt, bias, y, M, K, N, Np, Kp, s);
   constexpr int NT = 4, MT = 4;
   const int n_chunks = Np / (16 * NT);
@@ -2464,13 +2622,15 @@ hipError_t launch_x2_pw_relu(const void* x, const void* wt, const float* bias, f
 bool x2_pw_pool_supported(int HW, int N) { return HW % 64 == 0 && N % 64 == 0; }
 
 hipError_t launch_x2_pw_pool(const void* x, const void* wt, const float* bias, float* part, float* pooled, int B,
-                             int HW, int K, int N, hipStream_t s) {
+                             int HW, int K, int N, hipStream_t s, bool wide) {
   const int Kp = (K + 31) & ~31, Np = (N + 15) & ~15;
   if ((K & 7) || !x2_pw_pool_supported(HW, N) || B <= 0) return hipErrorInvalidValue;
   constexpr int NT = 4, MT = 4;
   const int64_t M = (int64_t)B * HW;
   hipError_t e;
-  if (x2_pws_ok(Kp, Np)) {
+  if (wide && x2_pws_wide_ok(Kp, Np)) {
+    e = x2_pws_wide_go<true>(x, wt, bias, part, M, K, N, Np, s);
+  } else if (x2_pws_ok(Kp, Np)) {
     e = x2_pws_go<true>(x, wt, bias, part, M, K, N, Np, Kp, s);
   } else {
     const int n_chunks = Np / (16 * NT);

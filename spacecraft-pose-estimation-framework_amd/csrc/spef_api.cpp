@@ -80,6 +80,7 @@ struct spef_ctx {
   int test_fail_bcast = 0;   // SPEF_OPT_TEST_FAIL_BCAST (spef_tuning.hpp): failure injection in spef_bcast_weights
   bool probe_f16 = false;    // run_backbone: the activation it stopped at is fp16 (fp16mx: blocks 1-3)
   int mx_kernels = 1;        // SPEF_OPT_MX_KERNELS (spef_tuning.hpp): fp16mx blocks 2-7 on k_mx.hip
+  int trim = 1;              // SPEF_OPT_TRIM (spef_tuning.hpp): bit 0 = the last conv's 128 x 320 tile
   // int8 blob: host copies of the FC quantisation constants, and their per-map-size device forms
   std::vector<double> q8_sw, q8_bias;
   std::vector<int32_t> q8_wsum;
@@ -504,7 +505,7 @@ int run_backbone(spef_ctx* c, const void* input, int layout, int B, int H, int W
         HIP_TRY(prof_launch(c, s, "x2_pw_kernel<pool>", M3 * op.cin * 4 + (double)op.cout * (op.cin * 4 + 4) +
                             (double)B * op.cout * 4, 2.0 * M3 * op.cin * op.cout, [&] {
           return launch_x2_pw_pool(cur, ptr<void>(c, op.w0), ptr<float>(c, op.b0), part, c->pooled, B, h * w,
-                                   (int)op.cin, (int)op.cout, s);
+                                   (int)op.cin, (int)op.cout, s, (c->trim & 1) != 0);
         }));
       } else if (x2) {   // fp32 map (keypoint head input, feature export, or the URSONet mean's input)
         float* y = (mode == 2 && feat_f32) ? feat_f32 : (float*)pick({cur});
@@ -512,7 +513,7 @@ int run_backbone(spef_ctx* c, const void* input, int layout, int B, int H, int W
         HIP_TRY(prof_launch(c, s, "x2_pw_kernel<4,4>", M3 * (op.cin + op.cout) * 4 + (double)op.cout * (op.cin * 4 + 4),
                             2.0 * M3 * op.cin * op.cout, [&] {
           return launch_x2_pw_relu(cur, ptr<void>(c, op.w0), ptr<float>(c, op.b0), y, (int64_t)B * h * w, (int)op.cin,
-                                   (int)op.cout, s);
+                                   (int)op.cout, s, (c->trim & 1) != 0);
         }));
         cur = y;
         ch = (int)op.cout;
@@ -2127,6 +2128,11 @@ int spef_set_option(spef_ctx* c, int option, int value) {
   }
   if (option == SPEF_OPT_MX_KERNELS) {   // spef_tuning.hpp
     c->mx_kernels = value ? 1 : 0;
+    return SPEF_OK;
+  }
+  if (option == SPEF_OPT_TRIM) {   // spef_tuning.hpp
+    if (value < 0 || value > 1) return fail(SPEF_ERR_ARG, "SPEF_OPT_TRIM: 0 or 1");
+    c->trim = value;
     return SPEF_OK;
   }
   if (option == SPEF_OPT_WAVESPEC) {

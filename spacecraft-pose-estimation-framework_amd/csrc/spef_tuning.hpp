@@ -9,6 +9,9 @@
 //                         (exercises the timeout -> ncclCommAbort path without a hung peer). 0 = off.
 //   SPEF_OPT_MX_KERNELS : fp16mx blocks 2-7 on the dedicated kernels of k_mx.hip (1, default) or on the fp16x2 slab
 //                         kernels with fp16 block I/O (0).
+//   SPEF_OPT_TRIM       : kernels that drop work the result does not need, bit-identical to the ones they replace (an
+//                         A/B switch, one bit per kernel). Bit 0: the fp16x2 / fp16mx last conv on the 128-pixel x
+//                         320-channel staged tile (k_x2.hip) instead of 64 x 256. Default 1; 0 runs the earlier kernel.
 #pragma once
 
 enum spef_tuning_option {
@@ -16,5 +19,6 @@ enum spef_tuning_option {
   SPEF_OPT_PW_GEMM = 3,
   SPEF_OPT_IRB_VARIANT = 4,
   SPEF_OPT_TEST_FAIL_BCAST = 5,
-  SPEF_OPT_MX_KERNELS = 8
+  SPEF_OPT_MX_KERNELS = 8,
+  SPEF_OPT_TRIM = 9
 };

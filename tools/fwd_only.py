@@ -1,4 +1,5 @@
-"""Minimal forward loop for counter collection: python tools/fwd_only.py [iters] (B=64, 512x512; DT=fp16|bf16|int8)."""
+"""Minimal forward loop for counter collection: python tools/fwd_only.py [iters] (B=64, 512x512; DT=fp16|bf16|int8|...;
+OPTS="9=0 8=1": spef_set_option pairs applied to the engine)."""
 import os
 import sys
 
@@ -22,6 +23,8 @@ if os.environ.get('DT') == 'int8':   # the C5 path, calibrated like bench.py --d
     eng = Engine(pack_int8(sd, calibrate(sd, synth_frames(4, 128, 128, 900))), 'cuda:0')
 else:
     eng = Engine(Bl.pack(sd, dtype=os.environ.get('DT', 'fp16')), 'cuda:0')
+for o in os.environ.get('OPTS', '').split():
+    eng.set_option(*(int(v) for v in o.split('=')))
 fr = torch.from_numpy(np.random.Generator(np.random.PCG64(0)).integers(0, 256, (B, S, S, 3), dtype=np.uint8)).cuda()
 for _ in range(it):
     eng.forward(fr)

@@ -1,6 +1,6 @@
 """Per-kernel forward time of one library build (SPEF_LIB) on the fp16mx headline workload (GPU box, development
 tool; no decode, so timing-ablation builds with wrong outputs run too): python tools/ktime.py [dtype] -> one JSON line
-{kernel: us per step}. tools/ktime.sh alternates builds."""
+{kernel: us per step}. tools/ktime.sh alternates builds. OPTS="9=0 8=1": spef_set_option pairs applied to the engine."""
 import json
 import os
 import sys
@@ -19,6 +19,8 @@ from spef_amd.weights import synthetic_state_dict
 dt = sys.argv[1] if len(sys.argv) > 1 else 'fp16mx'
 B, S, steps = int(os.environ.get('B', 64)), int(os.environ.get('S', 512)), int(os.environ.get('STEPS', 20))
 eng = Engine(Bl.pack(synthetic_state_dict(mobilenet_v2(), seed=1001), dtype=dt), 'cuda:0')
+for o in os.environ.get('OPTS', '').split():
+    eng.set_option(*(int(v) for v in o.split('=')))
 fr = torch.from_numpy(np.random.Generator(np.random.PCG64(0)).integers(0, 256, (B, S, S, 3), dtype=np.uint8)).cuda()
 for _ in range(10):
     eng.forward(fr)

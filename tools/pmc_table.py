@@ -11,7 +11,7 @@ from rocprof_summary import short_name  # noqa: E402
 
 root = sys.argv[1] if len(sys.argv) > 1 else 'gpurun_out'
 vals = defaultdict(lambda: defaultdict(list))
-for f in glob.glob(os.path.join(root, 'pmc_*', '*counter_collection.csv')):
+for f in glob.glob(os.path.join(root, 'pmc_*', '**', '*counter_collection.csv'), recursive=True):
     for r in csv.DictReader(open(f)):
         k = short_name(r['Kernel_Name'])
         if 'spef' not in r['Kernel_Name'] and 'irb' not in k:
@@ -21,7 +21,8 @@ mean = {k: {c: sum(v) / len(v) for c, v in d.items()} for k, d in vals.items()}
 cols = ['SQ_WAVES', 'SQ_WAVE_CYCLES', 'SQ_BUSY_CYCLES', 'SQ_WAIT_ANY', 'SQ_WAIT_INST_ANY', 'SQ_ACTIVE_INST_ANY',
         'SQ_ACTIVE_INST_VALU', 'SQ_ACTIVE_INST_LDS', 'SQ_ACTIVE_INST_VMEM', 'SQ_INSTS_VALU', 'SQ_INSTS_LDS',
         'SQ_INSTS_MFMA', 'SQ_INSTS_VMEM_RD', 'SQ_INSTS_SALU', 'SQ_LDS_BANK_CONFLICT', 'SQ_LDS_IDX_ACTIVE',
-        'SQ_VALU_MFMA_BUSY_CYCLES', 'GRBM_GUI_ACTIVE', 'FETCH_SIZE', 'WRITE_SIZE']
+        'SQ_VALU_MFMA_BUSY_CYCLES', 'GRBM_GUI_ACTIVE', 'FETCH_SIZE', 'WRITE_SIZE', 'TCP_TCC_READ_REQ_sum', 'TCC_REQ_sum',
+        'TCC_HIT_sum', 'TCC_MISS_sum']
 for k, d in sorted(mean.items()):
     wc = d.get('SQ_WAVE_CYCLES', 1)
     print(f'== {k}')
