@@ -13,6 +13,7 @@ import torch
 
 from oracle import decode_ref as D
 from oracle import model_ref as M
+from oracle.block_ref import oracle_block
 from spef_amd import blob as Bl
 from spef_amd.arch import mobilenet_v2
 from spef_amd.data.synthetic import synth_frames
@@ -29,6 +30,8 @@ F16_HIDDEN = range(2, 5)   # blocks whose expanded hidden tensor the schedule st
 
 
 def _frames(b, h, w, seed):
+    """H and W must be multiples of 4 (the blob pattern is 4x4-blocked); oracle/block_ref.py blob_frames is the same
+    generator for any size."""
     rng = np.random.Generator(np.random.PCG64(seed))
     base = rng.integers(0, 40, (b, h, w, 1), dtype=np.uint8)
     blob = rng.integers(0, 215, (b, h // 4, w // 4, 1), dtype=np.uint8).repeat(4, 1).repeat(4, 2)
@@ -38,31 +41,6 @@ def _frames(b, h, w, seed):
 def _sharp_sd():
     return synthetic_state_dict(mobilenet_v2('ursonet', 1728, 3), seed=1001, head_std=0.3, pos_std=0.01,
                                 pos_bias=(0.3, -0.2, 12.0))
-
-
-def _oracle_block(x, sd, idx, f16_hidden=F16_HIDDEN):
-    """features.features[idx] of the oracle (oracle/model_ref.py: the reference's float32 arithmetic, op for op) on
-    the activation x, with the schedule's fp16 hidden storage of blocks 2-4 restated (the expand output rounded to
-    fp16 before the depthwise); idx 0 = the stem."""
-    fp = 'features.features'
-    if idx == 0:
-        return M._conv_bn_act(x, sd, f'{fp}.0', 2, 1, True)
-    cin, i = 32, 1
-    for t, c, n, s in M._IR:
-        for k in range(n):
-            if i == idx:
-                stride = s if k == 0 else 1
-                y, j = x, 0
-                if t != 1:
-                    y = M._conv_bn_act(y, sd, f'{fp}.{idx}.conv.{j}', 1, 1, True)
-                    if idx in f16_hidden:
-                        y = y.half().float()
-                    j += 1
-                y = M._conv_bn_act(y, sd, f'{fp}.{idx}.conv.{j}', stride, int(round(cin * t)), True)
-                y = M._conv_bn_act(y, sd, f'{fp}.{idx}.conv.{j + 1}', 1, 1, False)
-                return x + y if (stride == 1 and cin == c) else y
-            cin, i = c, i + 1
-    raise ValueError(idx)
 
 
 @pytest.fixture(scope='module')
@@ -129,11 +107,11 @@ def test_block_outputs_vs_oracle(mx, sd, b, h, w, mx_kernels):
         for op in range(0, 18):
             got = mx.probe(xg, op).cpu()
             if op == 0:
-                ref = _oracle_block(x, sd, 0)
+                ref = oracle_block(x, sd, 0)
             elif op == 1:
-                ref = _oracle_block(_oracle_block(x, sd, 0), sd, 1)
+                ref = oracle_block(oracle_block(x, sd, 0), sd, 1)
             else:
-                ref = _oracle_block(prev.permute(0, 3, 1, 2).contiguous(), sd, op, f16_hidden)
+                ref = oracle_block(prev.permute(0, 3, 1, 2).contiguous(), sd, op, f16_hidden)
             if op in F16_BLOCKS:
                 ref = ref.half().float()
             ref = ref.permute(0, 2, 3, 1).numpy()

@@ -29,7 +29,8 @@ def _frames(b, h, w, seed):
     return f
 
 
-@pytest.mark.parametrize('src,dst', [((1200, 1920), (512, 512)), ((1200, 1920), (240, 384)), ((50, 70), (64, 96))])
+@pytest.mark.parametrize('src,dst', [((1200, 1920), (512, 512)), ((1200, 1920), (240, 384)), ((50, 70), (64, 96)),
+                                     ((1200, 1920), (101, 137)), ((51, 67), (99, 135))])   # odd targets, odd sources
 def test_resize_bit_exact_vs_pillow(engine, src, dst):
     eng, _ = engine
     fr = _frames(2, *src, seed=src[0] + dst[1])
@@ -52,5 +53,22 @@ def test_predict_frames_matches_host_resize(engine):
     small = np.stack([np.asarray(Image.fromarray(f).resize((512, 512), Image.BILINEAR)) for f in fr])
     pose_host, _ = spe.predict(torch.from_numpy(small))          # uint8 NHWC frames, same fused path
     assert lat > 0
+    for k in ('ori_soft', 'ori', 'pos'):
+        np.testing.assert_array_equal(pose_dev[k], pose_host[k])
+
+
+def test_predict_frames_to_odd_target_matches_host_resize(engine):
+    """The same at an odd target with W % 4 = 3 (99 x 135): the resize writes rows of 405 bytes and the front kernel
+    stages them at a different byte phase per row."""
+    from spef_amd.spe.spe_utils import SPEUtils
+    from spef_amd.spe_mi355x import SPEMi355x
+    eng, _ = engine
+    su = SPEUtils(None, 'classification', 12, 3, False, 'regression')
+    spe = SPEMi355x(eng, 'cuda:0', su)
+    fr = _frames(2, 300, 480, seed=6)
+    pose_dev, _ = spe.predict_frames(torch.from_numpy(fr), (99, 135))
+    small = np.stack([np.asarray(Image.fromarray(f).resize((135, 99), Image.BILINEAR)) for f in fr])
+    assert small.shape == (2, 99, 135, 3)
+    pose_host, _ = spe.predict(torch.from_numpy(small))
     for k in ('ori_soft', 'ori', 'pos'):
         np.testing.assert_array_equal(pose_dev[k], pose_host[k])

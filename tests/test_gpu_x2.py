@@ -23,6 +23,8 @@ X2_GOLDEN_TOL = 1e-4  # vs the reference's fixtures: split operands carry 22 sig
 
 
 def _frames(b, h, w, seed):
+    """H and W must be multiples of 4 (the blob pattern is 4x4-blocked); oracle/block_ref.py blob_frames is the same
+    generator for any size."""
     rng = np.random.Generator(np.random.PCG64(seed))
     base = rng.integers(0, 40, (b, h, w, 1), dtype=np.uint8)
     blob = rng.integers(0, 215, (b, h // 4, w // 4, 1), dtype=np.uint8).repeat(4, 1).repeat(4, 2)
