@@ -25,6 +25,8 @@
 //   project  three MFMAs per product (W_hi d_hi + W_lo d_hi + W_hi d_lo), fp32 accumulators across chunks; + residual
 //            (the block input) -> fp16 (blocks 2-3) or fp32 (blocks 4-7) NHWC.
 // Two barriers per chunk (slab ready; exchange ready).
+#include <type_traits>
+
 #include "spef_common.hpp"
 #include "spef_kernels.hpp"
 
@@ -46,6 +48,24 @@ __device__ __forceinline__ void b128_group(int lane, int& g, int& i) {
   g = gg + 2 * h;
   i = ii;
 }
+
+// The same map without branches (the lean set-up): by lane quad t = l / 4 the group bit is 0 1 1 0 1 0 0 1 and the
+// index l - 4 ((t + 1) / 2).
+__device__ __forceinline__ void b128_group_lean(int lane, int& g, int& i) {
+  const int l = lane & 31, t = l >> 2;
+  g = ((0x96 >> t) & 1) + 2 * (lane >> 5);
+  i = l - 4 * ((t + 1) >> 1);
+}
+constexpr bool b128_group_same() {   // (the branchy form restated: a constexpr check of the table above)
+  for (int l = 0; l < 32; ++l) {
+    const int t = l >> 2, gg = (0x96 >> t) & 1, ii = l - 4 * ((t + 1) >> 1);
+    const int rg = l < 4 ? 0 : l < 12 ? 1 : l < 16 ? 0 : l < 20 ? 1 : l < 28 ? 0 : 1;
+    const int ri = l < 4 ? l : l < 12 ? l - 4 : l < 20 ? l - 8 : l < 28 ? l - 12 : l - 16;
+    if (gg != rg || ii != ri) return false;
+  }
+  return true;
+}
+static_assert(b128_group_same(), "b128_group_lean");
 
 __device__ __forceinline__ uint32_t lo_pair_mx(uint32_t hi2, float a, float b) {
   uint32_t r;
@@ -91,7 +111,24 @@ struct MxGeom {
   static_assert(EPT <= 32, "validity mask");
 };
 
-template <int CIN, int HID, int COUT, int S, int TH, bool RES, bool IN16, bool OUT16>
+// pixel tile 0's row of a lane's tile pixel p < 64: p / IW as one 24-bit multiply (exact for p < 64, checked below)
+constexpr bool mx_div64_exact(int d) {
+  for (int p = 0; p < 64; ++p)
+    if (((p * (65536 / d + 1)) >> 16) != p / d) return false;
+  return true;
+}
+
+// LEAN (SPEF_OPT_TRIM bit 1): the tile set-up without the 64-bit per-pixel address arithmetic -- the same loads,
+// stores and sums, bit-identical to LEAN = false (the launcher takes it when an image's maps are below 2^31 bytes):
+//   * the image is a buffer resource (scalar base, 32-bit per-lane byte offsets); a pixel outside the image, a lane
+//     beyond the tile and a k group beyond CIN read at an offset past the resource, which returns zeros: no branch
+//     and no zero moves per tile;
+//   * (py, px) of a lane's pixel tiles by the compile-time step of 64 tile pixels with one carry select per tile,
+//     one division (a 24-bit multiply) for tile 0;
+//   * interior workgroups: no bounds checks, offsets by adds of two workgroup-uniform steps; edge workgroups:
+//     unsigned compares into the 32-bit zmask, the padding zeros stored by the chunk loop's restore code;
+//   * the epilogue's row bases are scalar, a lane adds one 32-bit offset.
+template <int CIN, int HID, int COUT, int S, int TH, bool RES, bool IN16, bool OUT16, bool LEAN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MxGeom<CIN, HID, COUT, S, TH>::WAVES_PER_EU)))
 void mx_irb_kernel(const void* __restrict__ X, const _Float16* __restrict__ We, const float* __restrict__ be,
                    const float* __restrict__ Wd, const float* __restrict__ bd, const _Float16* __restrict__ Wp,
@@ -131,34 +168,80 @@ void mx_irb_kernel(const void* __restrict__ X, const _Float16* __restrict__ We, 
   auto erow = [&](int h) { return 8 * (r16 >> 2) + 4 * h + (r16 & 3); };
   auto zero_slot = [&](int o) { *reinterpret_cast<uint4*>(smem + o) = make_uint4(0u, 0u, 0u, 0u); };
   int soff[G::EPT];   // slab byte offset of the lane's pixel (its first channel of h = 0), or its dummy row
+  if constexpr (LEAN) {
+    constexpr int CB = CIN * 2;                             // bytes per input pixel
+    constexpr int DY = 64 / G::IW, DX = 64 % G::IW;         // a lane's pixel tiles are 64 tile pixels apart
+    constexpr uint32_t OOB = 0x80000000u;                   // past every image (launcher): the load returns zeros
+    static_assert(mx_div64_exact(G::IW), "tile 0's row by multiply");
+    const int pitch = W * CB;                               // < 2^23 (launcher)
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char*>(reinterpret_cast<const char*>(X)) + (size_t)b * H * W * CB, 0, H * W * CB, 0x00020000);
+    auto ld = [&](uint32_t o) { return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(xr, o, 0, 0)); };
+    const int p0 = wave * 16 + r16;                         // the lane's pixel of tile j: p0 + 64 j
+    const int py = (int)(__umul24(p0, 65536 / G::IW + 1) >> 16), px = p0 - __mul24(py, G::IW);
+    const int kc = 8 * kg % KX;                             // the lane's first input channel
+    const uint32_t kco = kc < CIN ? 2u * kc : OOB;          // k groups beyond CIN read zeros
+    const int s0 = __mul24(p0, G::SPB) + KGB * kg, tr = G::OFF_TR + r16 * G::SPB + KGB * kg;
+    // the image pixel (iy, ix) of the lane's tile pixel and its byte offset, stepped from tile to tile: 64 tile pixels
+    // on are DY rows and DX columns, one row more and IW columns back where the column leaves the tile. The offset of
+    // a pixel outside the image is the same sum modulo 2^32 (signed 24-bit multiplies), never loaded from.
+    const uint32_t st = DY * pitch + DX * CB, sw = st + pitch - G::IW * CB;   // workgroup-uniform offset steps
+    const int ixe = ix0 + G::IW;
+    int iy = iy0 + py, ix = ix0 + px;
+    uint32_t off = (uint32_t)__mul24(iy, pitch) + (uint32_t)__mul24(ix, CB) + kco;
+    auto tiles = [&](auto chk) {
 #pragma unroll
-  for (int j = 0; j < G::EPT; ++j) {
-    const int p = (wave + G::NW * j) * 16 + r16;
-    bool ok = false;
-    int iy = 0, ix = 0;
-    if (p < G::PIN) {
-      const int py = p / G::IW, px = p - py * G::IW;
-      iy = iy0 + py;
-      ix = ix0 + px;
-      ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
+      for (int j = 0; j < G::EPT; ++j) {
+        const bool inb = 64 * j + 63 < G::PIN || p0 + 64 * j < G::PIN;   // compile-time but for the last tile
+        bool ok = inb;
+        if constexpr (decltype(chk)::value)   // (& not &&: selects, no branches)
+          ok = ok & ((unsigned)iy < (unsigned)H) & ((unsigned)ix < (unsigned)W);
+        bx[j] = ld(off | (ok ? 0u : OOB));   // (an or, not a select of offsets: the compiler branches around those)
+        soff[j] = ok ? s0 + 64 * j * G::SPB : tr;
+        if constexpr (decltype(chk)::value)   // zeroed by the chunk loop (every chunk: the exchange overlays the slab)
+          zmask |= (inb & !ok) ? 1u << j : 0u;
+        ix += DX;
+        const bool cy = ix >= ixe;
+        ix -= cy ? G::IW : 0;
+        off += cy ? sw : st;
+        if constexpr (decltype(chk)::value) iy += DY + (cy ? 1 : 0);
+      }
+    };
+    if (!edge) tiles(std::false_type{});   // interior workgroup: every tile pixel is in the image
+    else tiles(std::true_type{});
+  } else {
+#pragma unroll
+    for (int j = 0; j < G::EPT; ++j) {
+      const int p = (wave + G::NW * j) * 16 + r16;
+      bool ok = false;
+      int iy = 0, ix = 0;
+      if (p < G::PIN) {
+        const int py = p / G::IW, px = p - py * G::IW;
+        iy = iy0 + py;
+        ix = ix0 + px;
+        ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
+      }
+      const int kc = 8 * kg % KX;   // the lane's first input channel
+      const size_t e0 = xb + ((size_t)iy * W + ix) * CIN + kc;
+      {
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (ok && kc < CIN) v = *reinterpret_cast<const uint4*>(reinterpret_cast<const _Float16*>(X) + e0);
+        bx[j] = __builtin_bit_cast(f16x8, v);
+      }
+      const int ps = p;
+      if (!ok && p < G::PIN) zmask |= 1u << j;   // (re-zeroed every chunk on edge tiles: the exchange overlays the slab)
+      soff[j] = ok ? ps * G::SPB + KGB * kg : G::OFF_TR + r16 * G::SPB + KGB * kg;
+      if (!ok && p < G::PIN) zero_slot(ps * G::SPB + KGB * kg);   // the depthwise's zero padding
     }
-    const int kc = 8 * kg % KX;   // the lane's first input channel
-    const size_t e0 = xb + ((size_t)iy * W + ix) * CIN + kc;
-    {
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (ok && kc < CIN) v = *reinterpret_cast<const uint4*>(reinterpret_cast<const _Float16*>(X) + e0);
-      bx[j] = __builtin_bit_cast(f16x8, v);
-    }
-    const int ps = p;
-    if (!ok && p < G::PIN) zmask |= 1u << j;   // (re-zeroed every chunk on edge tiles: the exchange overlays the slab)
-    soff[j] = ok ? ps * G::SPB + KGB * kg : G::OFF_TR + r16 * G::SPB + KGB * kg;
-    if (!ok && p < G::PIN) zero_slot(ps * G::SPB + KGB * kg);   // the depthwise's zero padding
   }
 
   // ---- depthwise lane geometry: (row group ry, column cx) from the ds_read_b128 lane groups
   int ry, cx;
-  b128_group(lane, ry, cx);
-  const int dbase = (S * ry * G::PPL * G::IW + S * cx) * G::SPB + 16 * wave;   // input row 0, kx 0
+  if constexpr (LEAN) b128_group_lean(lane, ry, cx);
+  else b128_group(lane, ry, cx);
+  // LDS byte offsets are below 2^24: 24-bit multiplies in the lean set-up (full rate; the same products)
+  auto lmul = [](int a, int k) { return LEAN ? (int)__umul24(a, k) : a * k; };
+  const int dbase = lmul(S * ry * G::PPL * G::IW + S * cx, G::SPB) + 16 * wave;   // input row 0, kx 0
   constexpr int KXO[3] = {0, G::SPB, 2 * G::SPB};   // slab byte step of tap kx
   char* Dh = smem + G::OFF_DX;
   char* Dl = Dh + G::DX_B;
@@ -233,7 +316,7 @@ void mx_irb_kernel(const void* __restrict__ X, const _Float16* __restrict__ We, 
         *reinterpret_cast<uint4*>(smem + soff[j]) = make_uint4(relu_pk2(e[0][0], e[0][1]), relu_pk2(e[0][2], e[0][3]),
                                                                relu_pk2(e[1][0], e[1][1]), relu_pk2(e[1][2], e[1][3]));
       }
-      if (edge && c > 0) {   // the exchange overlaid the slab: restore the depthwise's zero padding
+      if (edge && (LEAN || c > 0)) {   // the exchange overlaid the slab: restore the depthwise's zero padding
 #pragma unroll
         for (int j = 0; j < G::EPT; ++j)
           if ((zmask >> j) & 1u) {
@@ -307,7 +390,7 @@ void mx_irb_kernel(const void* __restrict__ X, const _Float16* __restrict__ We, 
         ll[e] = lo_pair_mx(hh[e], x0, x1);
       }
       const int px = (ry * G::PPL + t) * TW + cx;
-      const int o = px * G::DXB + skw + 16 * wave;
+      const int o = (LEAN ? lmul(ry * G::PPL * TW + cx, G::DXB) + t * (TW * G::DXB) : px * G::DXB) + skw + 16 * wave;
       *reinterpret_cast<uint4*>(Dh + o) = make_uint4(hh[0], hh[1], hh[2], hh[3]);
       *reinterpret_cast<uint4*>(Dl + o) = make_uint4(ll[0], ll[1], ll[2], ll[3]);
     }
@@ -317,7 +400,9 @@ void mx_irb_kernel(const void* __restrict__ X, const _Float16* __restrict__ We, 
 #pragma unroll
     for (int i = 0; i < G::QPW; ++i) {
       const int q = wave * G::QPW + i;
-      const int o = (q * TW + r16) * G::DXB + ((q / G::PPL) & 1) * 16 + 16 * kg;
+      // (lean: the row's part is wave-uniform, the lane's part one multiply hoisted out of the loop)
+      const int o = (LEAN ? q * (TW * G::DXB) + lmul(r16, G::DXB) : (q * TW + r16) * G::DXB) +
+                    ((q / G::PPL) & 1) * 16 + 16 * kg;
       const f16x8 bh = *reinterpret_cast<const f16x8*>(Dh + o);
       const f16x8 bl = *reinterpret_cast<const f16x8*>(Dl + o);
 #pragma unroll
@@ -328,31 +413,60 @@ void mx_irb_kernel(const void* __restrict__ X, const _Float16* __restrict__ We, 
   }
 
   // ---- epilogue: + residual (fp16 block input, added after the BN bias, pytorch_layers.py:93-96)
+  if constexpr (LEAN) {
+    constexpr int OB = OUT16 ? 2 : 4;                         // bytes per output element
+    const uint32_t oo = (uint32_t)(r16 * COUT + 4 * kg) * OB, ro = (uint32_t)(r16 * CIN + 4 * kg) * 2;
+    if (ox0 + r16 < OW) {
 #pragma unroll
-  for (int i = 0; i < G::QPW; ++i) {
-    const int q = wave * G::QPW + i;
-    const int gy = oy0 + q, gx = ox0 + r16;
-    if (gy >= OH || gx >= OW) continue;
-    const size_t pix = ((size_t)b * OH + gy) * OW + gx;
+      for (int i = 0; i < G::QPW; ++i) {
+        const int gy = oy0 + wave * G::QPW + i;
+        if (gy >= OH) break;                                  // wave-uniform
+        const size_t pix = ((size_t)b * OH + gy) * OW + ox0;  // scalar: the row's first pixel of this tile
+        char* Yq = reinterpret_cast<char*>(Y) + pix * (COUT * OB);
+        const char* Xq = reinterpret_cast<const char*>(X) + pix * (CIN * 2);
 #pragma unroll
-    for (int t = 0; t < G::NCT; ++t) {
-      const int co = t * 16 + 4 * kg;
-      if (co >= COUT) continue;
-      f32x4 v = acc[i][t];
-      if constexpr (RES) {
-        const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const _Float16*>(X) + pix * CIN + co);
-        v[0] += h_lo(r.x); v[1] += h_hi(r.x); v[2] += h_lo(r.y); v[3] += h_hi(r.y);
+        for (int t = 0; t < G::NCT; ++t) {
+          if (t * 16 + 4 * kg >= COUT) continue;
+          f32x4 v = acc[i][t];
+          if constexpr (RES) {
+            const uint2 r = *reinterpret_cast<const uint2*>(Xq + (ro + t * 32));
+            v[0] += h_lo(r.x); v[1] += h_hi(r.x); v[2] += h_lo(r.y); v[3] += h_hi(r.y);
+          }
+          if constexpr (OUT16)
+            *reinterpret_cast<uint2*>(Yq + (oo + t * 16 * OB)) =
+                make_uint2(pack_h2((_Float16)v[0], (_Float16)v[1]), pack_h2((_Float16)v[2], (_Float16)v[3]));
+          else
+            *reinterpret_cast<float4*>(Yq + (oo + t * 16 * OB)) = make_float4(v[0], v[1], v[2], v[3]);
+        }
       }
-      if constexpr (OUT16)
-        *reinterpret_cast<uint2*>(reinterpret_cast<_Float16*>(Y) + pix * COUT + co) =
-            make_uint2(pack_h2((_Float16)v[0], (_Float16)v[1]), pack_h2((_Float16)v[2], (_Float16)v[3]));
-      else
-        *reinterpret_cast<float4*>(reinterpret_cast<float*>(Y) + pix * COUT + co) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < G::QPW; ++i) {
+      const int q = wave * G::QPW + i;
+      const int gy = oy0 + q, gx = ox0 + r16;
+      if (gy >= OH || gx >= OW) continue;
+      const size_t pix = ((size_t)b * OH + gy) * OW + gx;
+#pragma unroll
+      for (int t = 0; t < G::NCT; ++t) {
+        const int co = t * 16 + 4 * kg;
+        if (co >= COUT) continue;
+        f32x4 v = acc[i][t];
+        if constexpr (RES) {
+          const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const _Float16*>(X) + pix * CIN + co);
+          v[0] += h_lo(r.x); v[1] += h_hi(r.x); v[2] += h_lo(r.y); v[3] += h_hi(r.y);
+        }
+        if constexpr (OUT16)
+          *reinterpret_cast<uint2*>(reinterpret_cast<_Float16*>(Y) + pix * COUT + co) =
+              make_uint2(pack_h2((_Float16)v[0], (_Float16)v[1]), pack_h2((_Float16)v[2], (_Float16)v[3]));
+        else
+          *reinterpret_cast<float4*>(reinterpret_cast<float*>(Y) + pix * COUT + co) = make_float4(v[0], v[1], v[2], v[3]);
+      }
     }
   }
 }
 
-template <int CIN, int HID, int COUT, int S, int TH, bool RES, bool IN16, bool OUT16>
+template <int CIN, int HID, int COUT, int S, int TH, bool RES, bool IN16, bool OUT16, bool LEAN>
 static hipError_t mx_go(const void* x, const void* we, const float* be, const float* wd, const float* bd,
                         const void* wp, const float* bp, void* y, int B, int H, int W, int OH, int OW, hipStream_t s) {
   using G = MxGeom<CIN, HID, COUT, S, TH>;
@@ -360,7 +474,7 @@ static hipError_t mx_go(const void* x, const void* we, const float* be, const fl
   const int64_t nwg64 = (int64_t)tiles_x * tiles_y * B;
   if (nwg64 > 0x7fffffff) return hipErrorInvalidValue;
   const uint32_t nwg = (uint32_t)nwg64;
-  auto k = mx_irb_kernel<CIN, HID, COUT, S, TH, RES, IN16, OUT16>;
+  auto k = mx_irb_kernel<CIN, HID, COUT, S, TH, RES, IN16, OUT16, LEAN>;
   if (G::LDS_BYTES > 65536) {
     static DevOnce attr_set;   // per device
     if (!attr_set.done()) {
@@ -393,14 +507,24 @@ bool mx_irb_supported(int cin, int hid, int cout, int stride, bool expand, bool 
   return false;
 }
 
+// The lean set-up's 32-bit offsets: one image's input map and output map below 2^31 bytes (a lane's byte offset into
+// its image; an offset of 2^31 or more reads zeros), the input row pitch and the row index below 2^23 (signed
+// 24-bit multiplies). A map beyond that runs the kernel with 64-bit per-pixel addresses.
+bool mx_irb_lean_fits(int cin, int cout, bool out16, int H, int W, int OH, int OW) {
+  return (int64_t)H * W * cin * 2 <= 0x7fffffff && (int64_t)OH * OW * cout * (out16 ? 2 : 4) <= 0x7fffffff &&
+         (int64_t)W * cin * 2 < (1 << 23) && H < (1 << 23);
+}
+
 hipError_t launch_mx_irb(int cin, int hid, int cout, int stride, bool res, bool in16, bool out16, const void* x,
                          const void* we,
                          const float* be, const float* wd, const float* bd, const void* wp, const float* bp, void* y,
-                         int B, int H, int W, int OH, int OW, hipStream_t s) {
+                         int B, int H, int W, int OH, int OW, hipStream_t s, bool lean) {
   if (!x || !y || !we || !be || !wd || !bd || !wp || !bp) return hipErrorInvalidValue;
+  lean = lean && mx_irb_lean_fits(cin, cout, out16, H, W, OH, OW);
 #define SPEF_MX_CASE(CI, HI, CO, ST, RS, I16, O16, TH_)                                                  \
   if (cin == CI && hid == HI && cout == CO && stride == ST && res == RS && in16 == I16 && out16 == O16)  \
-    return mx_go<CI, HI, CO, ST, TH_, RS, I16, O16>(x, we, be, wd, bd, wp, bp, y, B, H, W, OH, OW, s);
+    return lean ? mx_go<CI, HI, CO, ST, TH_, RS, I16, O16, true>(x, we, be, wd, bd, wp, bp, y, B, H, W, OH, OW, s)  \
+                : mx_go<CI, HI, CO, ST, TH_, RS, I16, O16, false>(x, we, be, wd, bd, wp, bp, y, B, H, W, OH, OW, s);
   SPEF_MX_TABLE(SPEF_MX_CASE)
 #undef SPEF_MX_CASE
   return hipErrorNotSupported;

@@ -80,7 +80,8 @@ struct spef_ctx {
   int test_fail_bcast = 0;   // SPEF_OPT_TEST_FAIL_BCAST (spef_tuning.hpp): failure injection in spef_bcast_weights
   bool probe_f16 = false;    // run_backbone: the activation it stopped at is fp16 (fp16mx: blocks 1-3)
   int mx_kernels = 1;        // SPEF_OPT_MX_KERNELS (spef_tuning.hpp): fp16mx blocks 2-7 on k_mx.hip
-  int trim = 1;              // SPEF_OPT_TRIM (spef_tuning.hpp): bit 0 = the last conv's 128 x 320 tile
+  int trim = 3;              // SPEF_OPT_TRIM (spef_tuning.hpp): bit 0 = the last conv's 128 x 320 tile, bit 1 = the
+                             // lean tile set-up of mx_irb_kernel
   // int8 blob: host copies of the FC quantisation constants, and their per-map-size device forms
   std::vector<double> q8_sw, q8_bias;
   std::vector<int32_t> q8_wsum;
@@ -394,7 +395,10 @@ int run_backbone(spef_ctx* c, const void* input, int layout, int B, int H, int W
         const bool mxk = mx && c->mx_kernels &&
                          mx_irb_supported((int)op.cin, (int)op.hidden, (int)op.cout, (int)op.stride, expand, res, cur16,
                                           o16);
-        const char* kn = mxk ? "mx_irb_kernel"
+        // "_wide": the lean set-up was asked for and a map is too large for its 32-bit offsets
+        const bool mxlean = (c->trim & 2) != 0;
+        const char* kn = mxk ? (mxlean && !mx_irb_lean_fits((int)op.cin, (int)op.cout, o16, h, w, OH, OW)
+                                    ? "mx_irb_kernel_wide" : "mx_irb_kernel")
                              : x2_irb_kernel_name((int)op.cin, (int)op.hidden, (int)op.cout, (int)op.stride, expand,
                                                   res, B, OH, OW, true, io, num_cus());
         snprintf(key, sizeof(key), "%s<%u,%u,%u,s%u>", kn ? kn : "x2_irb_kernel", op.cin, op.hidden, op.cout,
@@ -403,7 +407,7 @@ int run_backbone(spef_ctx* c, const void* input, int layout, int B, int H, int W
           if (mxk)
             return launch_mx_irb((int)op.cin, (int)op.hidden, (int)op.cout, (int)op.stride, res, cur16, o16, x,
                                  ptr<void>(c, op.w0), ptr<float>(c, op.b0), ptr<float>(c, op.w1), ptr<float>(c, op.b1),
-                                 ptr<void>(c, op.w2), ptr<float>(c, op.b2), y, B, h, w, OH, OW, s);
+                                 ptr<void>(c, op.w2), ptr<float>(c, op.b2), y, B, h, w, OH, OW, s, mxlean);
           // a third activation buffer (each holds the largest map) is the hidden-split form's partial-sum scratch
           return launch_x2_irb((int)op.cin, (int)op.hidden, (int)op.cout, (int)op.stride, expand, res, x,
                                ptr<void>(c, op.w0), ptr<float>(c, op.b0), ptr<float>(c, op.w1), ptr<float>(c, op.b1),
@@ -2131,7 +2135,7 @@ int spef_set_option(spef_ctx* c, int option, int value) {
     return SPEF_OK;
   }
   if (option == SPEF_OPT_TRIM) {   // spef_tuning.hpp
-    if (value < 0 || value > 1) return fail(SPEF_ERR_ARG, "SPEF_OPT_TRIM: 0 or 1");
+    if (value < 0 || value > 3) return fail(SPEF_ERR_ARG, "SPEF_OPT_TRIM: bits 0-1");
     c->trim = value;
     return SPEF_OK;
   }

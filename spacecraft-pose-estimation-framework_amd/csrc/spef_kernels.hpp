@@ -104,7 +104,10 @@ bool mx_irb_supported(int cin, int hid, int cout, int stride, bool expand, bool 
 hipError_t launch_mx_irb(int cin, int hid, int cout, int stride, bool res, bool in16, bool out16, const void* x,
                          const void* we,
                          const float* be, const float* wd, const float* bd, const void* wp, const float* bp, void* y,
-                         int B, int H, int W, int OH, int OW, hipStream_t s);
+                         int B, int H, int W, int OH, int OW, hipStream_t s, bool lean = true);
+// lean (SPEF_OPT_TRIM bit 1): the tile set-up on scalar bases and 32-bit offsets (same sums), taken where
+// mx_irb_lean_fits: an image's input and output maps below 2^31 bytes, the input row pitch and H below 2^23.
+bool mx_irb_lean_fits(int cin, int cout, bool out16, int H, int W, int OH, int OW);
 // fp16mx front (k_mx.hip front_mx_kernel): uint8 NHWC -> stem + block 1 -> fp16 [B][OH][OW][16]; wsp = OP_STEM x1.
 hipError_t launch_mx_front(const void* x, const void* wsp, const float* bs, const float* wd, const float* bd,
                            const void* wp, const float* bp, void* y, int B, int H, int W, int OH, int OW,

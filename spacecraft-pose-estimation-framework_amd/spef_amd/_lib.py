@@ -18,7 +18,9 @@ METRIC_IDS = {'l2': 0, 'kl': 1, 'js': 2, 'hellinger': 3, 'tv': 4, 'wasserstein':
 OPT_FUSE_BLOCKS, OPT_WAVESPEC, OPT_Q8_ROLESPLIT = 1, 6, 7     # public schedule options (include/spef.h)
 OPT_FUSE_MIN_HW, OPT_PW_GEMM, OPT_IRB_VARIANT, OPT_TEST_FAIL_BCAST = 2, 3, 4, 5   # internal (csrc/spef_tuning.hpp)
 OPT_MX_KERNELS = 8   # internal: fp16mx blocks 2-7 on k_mx.hip (1) or the fp16x2 slab kernels (0)
-OPT_TRIM = 9         # internal: bit 0 = the last conv's 128 x 320 tile (default 1; 0 = the earlier 64 x 256 kernel)
+OPT_TRIM = 9         # internal, one bit per kernel (a cleared bit runs the earlier kernel): bit 0 = the last conv's
+#                      128 x 320 tile (0: 64 x 256), bit 1 = mx_irb_kernel's lean tile set-up (0: 64-bit addresses)
+OPT_TRIM_DEFAULT = 3
 
 # name -> (restype, argtypes); keep in sync with include/spef.h (tests/test_abi.py checks the header)
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
