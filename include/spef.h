@@ -272,6 +272,34 @@ int spef_set_keypoint_distortion(spef_ctx* ctx, const double* dist, int n);
 int spef_decode_keypoints(spef_ctx* ctx, const float* raw, int B, int apply_sigmoid, float* kp_out, float* quat,
                           float* pos, int* status, void* stream);
 
+/* Robust pose refinement behind EPnP (opt-in; nothing calls it unless asked): Levenberg-Marquardt on the reprojection
+ * error over the pose itself, R <- exp([w]x) R, t <- t + dt, in fp64, on the observations spef_decode_keypoints solves
+ * on (float32 pixels, origin dropped, undistorted when distortion is configured; pinhole K).
+ *   kp        [B x 2(n+1)] normalised keypoints after the sigmoid (spef_decode_keypoints' kp_out).
+ *   weights   NULL or [B x n] per-point confidences c_i >= 0 (NULL: all 1).
+ *   huber_px  Huber threshold in pixels on the point's residual norm e_i; 0 = plain least squares. Loss: c_i e_i^2 up
+ *             to the threshold, c_i (2 d e_i - d^2) beyond (IRLS weight c_i d / e_i).
+ *   quat_inout / pos_inout  the start pose (EPnP's, the classification head's or the previous frame's), replaced by the
+ *             refined one; the quaternion keeps the start's hemisphere. A problem in which no trial was accepted keeps
+ *             its input bit for bit.
+ *   Damping starts at 1e-3, x 1/10 (floor 1e-9) on an accepted trial, x 10 otherwise; a trial is accepted only when the
+ *   cost falls strictly and every point stays in front of the camera. Stops on a step below 1e-10 (rad, and relative to
+ *   |t|), damping above 1e12, or after max_iters trials (1..100).
+ *   fit   [B x 4] (may be NULL): unweighted reprojection RMS in px before / after, minimised cost before / after.
+ *   cov   [B x 36] (may be NULL): row-major 6 x 6 pose covariance s^2 (J^T W J)^-1 at the final pose, order
+ *         (w_x, w_y, w_z, t_x, t_y, t_z), s^2 = cost_after / max(2 m - 6, 1), m = points with c_i > 0; NaN when the
+ *         normal matrix is singular.
+ *   iters [B] (may be NULL): trials run.
+ *   status [B] is ORed into, not cleared: bit 16 = not refined, the pose is untouched and fit / cov are NaN (the row
+ *         carries bit 8; a non-finite keypoint, weight or pose; a negative weight; a point at Z <= 0; fewer than 3
+ *         points with c_i > 0), bit 32 = stopped at max_iters (the pose is the best accepted one).
+ * Uses the model, camera and distortion of spef_set_keypoints / spef_set_keypoint_distortion (SPEF_ERR_STATE when not
+ * set). SPEF_ERR_ARG: a null required pointer, B <= 0, max_iters outside 1..100, huber_px negative or not finite.
+ * No allocation, no host synchronisation: it can follow spef_decode_keypoints on the same stream. */
+int spef_refine_keypoints(spef_ctx* ctx, const float* kp, const float* weights, int B, int max_iters, float huber_px,
+                          float* quat_inout, float* pos_inout, float* fit, float* cov, int* iters, int* status,
+                          void* stream);
+
 /* Input preprocessing on the device (SPEDataset.__getitem__ + transforms.Resize(img_size), utils.py:212-249,
  * speed.py:66-69): decoded frames uint8 [B x Hin x Win x 3] (RGB, HWC) -> uint8 [B x H x W x 3], bit-identical to
  * Pillow's Image.resize((W, H), BILINEAR). The result feeds spef_forward with SPEF_IN_U8_NHWC (ToTensor's /255

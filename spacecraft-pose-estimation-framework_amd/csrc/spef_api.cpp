@@ -2021,6 +2021,25 @@ int spef_decode_keypoints(spef_ctx* c, const float* raw, int B, int apply_sigmoi
   return SPEF_OK;
 }
 
+int spef_refine_keypoints(spef_ctx* c, const float* kp, const float* weights, int B, int max_iters, float huber_px,
+                          float* quat_inout, float* pos_inout, float* fit, float* cov, int* iters, int* status,
+                          void* stream) {
+  if (!c || !kp || !quat_inout || !pos_inout || !status || B <= 0) return fail(SPEF_ERR_ARG, "null argument");
+  if (max_iters < 1 || max_iters > 100) return fail(SPEF_ERR_ARG, "max_iters must be in 1..100");
+  if (!(huber_px >= 0.0f) || !std::isfinite(huber_px)) return fail(SPEF_ERR_ARG, "huber_px must be finite and >= 0");
+  if (!c->kp3d) return fail(SPEF_ERR_STATE, "keypoints not configured (spef_set_keypoints)");
+  Dev d(c->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int n = c->kp_n;
+  HIP_TRY(prof_launch(c, s, "refine_kernel", (double)B * ((2 * (n + 1) + (weights ? n : 0)) * 4 + 2 * 28 + 8 +
+                                                          (fit ? 16 : 0) + (cov ? 144 : 0) + (iters ? 4 : 0)),
+                      (double)B * 8.0 * n * 180.0, [&] {
+    return launch_refine(kp, weights, B, n, c->kp3d, c->camK, c->cam_nu, c->cam_nv, c->kp_dist, max_iters, huber_px,
+                         quat_inout, pos_inout, fit, cov, iters, status, s);
+  }));
+  return SPEF_OK;
+}
+
 // Pillow precompute_coeffs + normalize_coeffs_8bpc (libImaging/Resample.c), BILINEAR filter (support 1):
 // bounds [out][2] = (xmin, count), coefficients [out][ksize] in fixed point with 22 fractional bits.
 static int pil_coeffs(int in_size, int out_size, std::vector<int>& bounds, std::vector<int>& kk) {

@@ -143,6 +143,12 @@ struct EpnpDist {
 hipError_t launch_epnp(const float* raw, int B, int n, const float* kp3d, const double* model, const double* K,
                        float nu, float nv, const EpnpDist& dist, int apply_sigmoid, float* kp_out, float* quat,
                        float* pos, int* status, hipStream_t s);
+// Pose refinement behind EPnP (k_refine.hip): robust Levenberg-Marquardt on the reprojection error, in place on quat /
+// pos. kp: B x 2(n+1) normalised keypoints (after the sigmoid); weights: null or B x n; fit [B x 4], cov [B x 36] and
+// iters [B] may be null. status |= 16 (not refined), 32 (stopped at max_iters).
+hipError_t launch_refine(const float* kp, const float* weights, int B, int n, const float* kp3d, const double* K,
+                         float nu, float nv, const EpnpDist& dist, int max_iters, float huber_px, float* quat,
+                         float* pos, float* fit, float* cov, int* iters, int* status, hipStream_t s);
 
 // Activation dtype -> fp32 NHWC copy (debug probes / backbone feature export).
 hipError_t launch_to_f32(int dtype, const void* x, float* y, int64_t n, hipStream_t s);

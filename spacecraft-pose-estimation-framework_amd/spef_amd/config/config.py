@@ -21,7 +21,9 @@ DEFAULTS: Dict[str, Any] = {
         'BACKBONE': {'NAME': 'mobilenet_v2_pytorch', 'RESIDUAL': True},
         'HEAD': {'NAME': 'ursonet_pytorch', 'ORI': 'classification', 'POS': 'regression',
                  'N_ORI_BINS_PER_DIM': 12, 'N_POS_BINS_PER_DIM': 10, 'ORI_DELETE_UNUSED_BINS': False,
-                 'KEYPOINTS_PATH': 'models/3d_models/tangoPoints.mat'},
+                 'KEYPOINTS_PATH': 'models/3d_models/tangoPoints.mat',
+                 # this target: pose refinement behind EPnP (spe/refine.py, csrc/k_refine.hip); 0 trials = off
+                 'KEYPOINTS_REFINE_ITERS': 0, 'KEYPOINTS_REFINE_HUBER_PX': 0.0},
     },
     'DATA': {'BATCH_SIZE': 8, 'PATH': '../datasets/speed', 'IMG_SIZE': (240, 384), 'ORI_SMOOTH_FACTOR': 3,
              'POS_SMOOTH_FACTOR': 100, 'ROT_AUGMENT': True, 'OTHER_AUGMENT': True, 'SHUFFLE': True},
@@ -84,6 +86,7 @@ def load_config(path: str | None = None) -> Config:
     if h['ORI'] == 'keypoints' or h['POS'] == 'keypoints':
         assert h['ORI'] == 'keypoints' and h['POS'] == 'keypoints', \
             "Both ORI and POS must be 'keypoints' if one is 'keypoints'"
+    assert 0 <= h['KEYPOINTS_REFINE_ITERS'] <= 100 and h['KEYPOINTS_REFINE_HUBER_PX'] >= 0
     assert cfg['MI355X']['DTYPE'] in ('fp16mx', 'fp16', 'bf16', 'int8', 'fp32', 'fp16x2')
     assert cfg['MI355X']['CALIB_METHOD'] in ('percentile', 'mse', 'max')
     return _wrap(cfg)
@@ -105,3 +108,9 @@ def to_spe_utils(cfg: Config, camera=None, keypoints=None):
     kp = keypoints if keypoints is not None else (h.KEYPOINTS_PATH if h.ORI == 'keypoints' else None)
     return SPEUtils(camera, h.ORI, h.N_ORI_BINS_PER_DIM, d.ORI_SMOOTH_FACTOR, h.ORI_DELETE_UNUSED_BINS, h.POS,
                     h.N_POS_BINS_PER_DIM, d.POS_SMOOTH_FACTOR, kp)
+
+
+def keypoint_refine(cfg: Config):
+    """``SPEMi355x``'s ``keypoint_refine`` argument from MODEL.HEAD.KEYPOINTS_REFINE_*: (trials, Huber px) or None."""
+    h = cfg.MODEL.HEAD
+    return (int(h.KEYPOINTS_REFINE_ITERS), float(h.KEYPOINTS_REFINE_HUBER_PX)) if h.KEYPOINTS_REFINE_ITERS else None

@@ -279,6 +279,7 @@ class Engine:
         self.ctx = h
         self._reserved = (0, 0, 0)
         self._decode_tables = None
+        self._kp_refine = None      # (max_iters, huber_px) of set_keypoint_refine, or None: off
         # bumped by every call that moves device buffers or changes what a recorded forward / decode would do
         # (workspace reallocation, weights, decode tables, options, camera): StreamPipeline's recorded HIP graphs key on it
         self.epoch = 0
@@ -449,7 +450,59 @@ class Engine:
         status = torch.empty((B,), dtype=torch.int32, device=dev)
         L.check(self.lib.spef_decode_keypoints(self.ctx, _ptr(raw), B, 1 if apply_sigmoid else 0, _ptr(kp), _ptr(quat),
                                                _ptr(pos), _ptr(status), _stream(dev)))
-        return {'keypoints': kp, 'ori': quat, 'pos': pos, 'status': status}
+        dec = {'keypoints': kp, 'ori': quat, 'pos': pos, 'status': status}
+        refine = self._kp_refine
+        if refine is not None:   # set_keypoint_refine: Levenberg-Marquardt behind EPnP, same stream
+            ref = self.refine_keypoints(kp, quat, pos, max_iters=refine[0], huber_px=refine[1], status=status)
+            dec.update(ori=ref['ori'], pos=ref['pos'], ori_epnp=quat, pos_epnp=pos, fit=ref['fit'],
+                       refine_iters=ref['iters'])
+        return dec
+
+    def set_keypoint_refine(self, max_iters=None, huber_px: float = 0.0) -> None:
+        """Turn the pose refinement behind EPnP on (``max_iters`` trials in 1..100, Huber threshold ``huber_px`` in
+        pixels, 0 = plain least squares) or off (``max_iters`` 0 or None, the default). With it on,
+        ``decode_keypoints`` returns the refined 'ori' / 'pos' and adds 'ori_epnp', 'pos_epnp', 'fit' and
+        'refine_iters'; 'status' may carry the informational bits 16 (row not refined) and 32 (stopped at
+        ``max_iters``)."""
+        if not max_iters:
+            self._kp_refine = None
+            return
+        max_iters, huber_px = int(max_iters), float(huber_px)
+        assert 1 <= max_iters <= 100, 'max_iters must be in 1..100'
+        assert np.isfinite(huber_px) and huber_px >= 0, 'huber_px must be finite and >= 0'
+        self._kp_refine = (max_iters, huber_px)
+
+    def refine_keypoints(self, kp: torch.Tensor, quat: torch.Tensor, pos: torch.Tensor, weights=None,
+                         max_iters: int = 50, huber_px: float = 0.0, want_cov: bool = False, status=None) -> dict:
+        """Robust Levenberg-Marquardt refinement (csrc/k_refine.hip; ``spe.refine.refine_pose_host`` is its NumPy
+        twin) of the poses ``quat`` [B x 4] / ``pos`` [B x 3] -- EPnP's, a classification head's, the previous
+        frame's -- against the normalised keypoints ``kp`` [B x 2(n+1)] (after the sigmoid), with optional per-point
+        confidences ``weights`` [B x n]. The inputs are left as they are. -> {'ori', 'pos', 'fit' [B x 4]: RMS px
+        before / after, cost before / after, 'iters', 'status'} and, with ``want_cov``, 'cov' [B x 6 x 6] (order
+        omega_xyz, t_xyz). ``status`` [B] int32, when given, is ORed into in place (EPnP's word: a row with bit 8 is
+        not refined)."""
+        B = kp.shape[0]
+        dev = self.device
+        assert kp.dtype == torch.float32 and kp.is_contiguous() and kp.dim() == 2
+        q = quat.detach().to(dev, torch.float32).reshape(B, 4).clone()
+        t = pos.detach().to(dev, torch.float32).reshape(B, 3).clone()
+        w = None
+        if weights is not None:
+            w = weights.detach().to(dev, torch.float32).contiguous()
+            assert w.dim() == 2 and w.shape[0] == B and 2 * (w.shape[1] + 1) == kp.shape[1]
+        fit = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        cov = torch.empty((B, 6, 6), dtype=torch.float32, device=dev) if want_cov else None
+        iters = torch.empty((B,), dtype=torch.int32, device=dev)
+        if status is None:
+            status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() == B
+        L.check(self.lib.spef_refine_keypoints(self.ctx, _ptr(kp), _ptr(w), B, int(max_iters), float(huber_px),
+                                               _ptr(q), _ptr(t), _ptr(fit), _ptr(cov), _ptr(iters), _ptr(status),
+                                               _stream(dev)))
+        out = {'ori': q, 'pos': t, 'fit': fit, 'iters': iters, 'status': status}
+        if want_cov:
+            out['cov'] = cov
+        return out
 
     # ------------------------------------------------------------------ profiling
     def profile_begin(self) -> None:

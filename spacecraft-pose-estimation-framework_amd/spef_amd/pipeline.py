@@ -169,10 +169,16 @@ class StreamPipeline:
         for e in self.engines:
             e.set_keypoints(kp3d, K, nu, nv, dist)
 
+    def set_keypoint_refine(self, max_iters=None, huber_px: float = 0.0) -> None:
+        """``Engine.set_keypoint_refine`` on every slot: ``submit_keypoints`` (and the scorer behind it) then use the
+        pose refined behind EPnP. ``max_iters`` 0 or None turns it off."""
+        for e in self.engines:
+            e.set_keypoint_refine(max_iters, huber_px)
+
     def submit_keypoints(self, frames: torch.Tensor, score=None) -> dict:
-        """Keypoint mode: forward (KeypointRegressionHead) + sigmoid + batched EPnP of one batch on the next stream;
-        returns the decode dict of Engine.decode_keypoints plus 'raw' and 'event' (as submit()). ``score``: as in
-        ``submit``."""
+        """Keypoint mode: forward (KeypointRegressionHead) + sigmoid + batched EPnP (+ the pose refinement, when
+        ``set_keypoint_refine`` turned it on) of one batch on the next stream; returns the decode dict of
+        Engine.decode_keypoints plus 'raw' and 'event' (as submit()). ``score``: as in ``submit``."""
         i = self._next
         self._next = (i + 1) % self.depth
         eng, s = self.engines[i], self.streams[i]
@@ -186,7 +192,12 @@ class StreamPipeline:
         dec['raw'] = raw
         dec['event'] = ev
         if score is not None:
-            self._score(s, dec, score)
+            scored = dec
+            if 'ori_epnp' in dec:   # the refinement's bits 16 / 32 are informational, not decode failures
+                with torch.cuda.stream(s):
+                    scored = dict(dec, status=dec['status'] & 15)
+            self._score(s, scored, score)
+            dec['event'] = scored['event']
         return dec
 
     def synchronize(self) -> None:

@@ -34,10 +34,15 @@ class SPEMi355x:
         device: HIP device (``cuda:N``).
         spe_utils: the reference ``SPEUtils`` (or ``spef_amd.spe.spe_utils.SPEUtils``): provides ori/pos mode
             and the decode histograms.
+        keypoint_refine: None (off) or ``(max_iters, huber_px)``: keypoint mode refines EPnP's pose by robust
+            Levenberg-Marquardt on the GPU (``Engine.set_keypoint_refine``); ``predict`` then returns the refined
+            'ori' / 'pos' and adds 'ori_epnp', 'pos_epnp' and 'reproj_rms' (px, before / after).
     """
 
-    def __init__(self, model: Union[bytes, str, Engine], device: Union[str, torch.device], spe_utils) -> None:
+    def __init__(self, model: Union[bytes, str, Engine], device: Union[str, torch.device], spe_utils,
+                 keypoint_refine=None) -> None:
         self.spe_utils = spe_utils
+        self.keypoint_refine = tuple(keypoint_refine) if keypoint_refine and keypoint_refine[0] else None
         self.device = torch.device(device)
         self.engine = None
         self._video = None          # (configuration, VideoFilter) of predict_video
@@ -70,6 +75,8 @@ class SPEMi355x:
                                       float(cam.nu), float(cam.nv), getattr(cam, 'distCoeffs', None))
             if self.engine.n_out0 != 2 * (kp.keypoints3d.shape[0] + 1):   # model.py:236
                 raise AssertionError(f'keypoint head width {self.engine.n_out0} != 2 * (n_keypoints + 1)')
+            if self.keypoint_refine is not None:
+                self.engine.set_keypoint_refine(*self.keypoint_refine)
             return
         ori_bins = su.orientation.histogram if self.ori_mode == L.CLASSIFICATION else None
         pos_grid = su.position.histogram if self.pos_mode == L.CLASSIFICATION else None
@@ -159,6 +166,8 @@ class SPEMi355x:
                 kp, kk, dd = self.engine._kp
                 cam = self.spe_utils.keypoints.camera
                 self._pipe.set_keypoints(kp, kk.reshape(3, 3), float(cam.nu), float(cam.nv), dd if dd.size else None)
+                if self.keypoint_refine is not None:
+                    self._pipe.set_keypoint_refine(*self.keypoint_refine)
         return self._pipe
 
     def _close_pipe(self) -> None:
@@ -217,9 +226,15 @@ class SPEMi355x:
         if np.any(status & 8):
             raise ValueError('EPnP failed on a batch row (degenerate keypoints)')   # cv2.solvePnP error analogue
 
+        # bits 16 (row not refined) and 32 (refinement stopped at max_iters) are informational: the pose stands
         if self.keypoint_mode:
-            return {'keypoints': dec['keypoints'].cpu().numpy(), 'ori': dec['ori'].cpu().numpy(),
+            pose = {'keypoints': dec['keypoints'].cpu().numpy(), 'ori': dec['ori'].cpu().numpy(),
                     'pos': dec['pos'].cpu().numpy()}
+            if 'ori_epnp' in dec:   # keypoint_refine
+                pose['ori_epnp'] = dec['ori_epnp'].cpu().numpy()
+                pose['pos_epnp'] = dec['pos_epnp'].cpu().numpy()
+                pose['reproj_rms'] = dec['fit'][:, :2].cpu().numpy()
+            return pose
 
         pose = {'ori': dec['ori'].cpu().numpy(), 'pos': dec['pos'].cpu().numpy()}
         if self.ori_mode == L.CLASSIFICATION:

@@ -1,6 +1,10 @@
 """``evaluation()`` on this target: the reference's loop (src/tools/evaluation.py:36-100) -- same running
 averages, same score/error records (ESA score via SPEUtils.get_score, std and median absolute deviation of the
-per-image errors) -- driving any object with ``predict(images) -> (pose, latency_ms)`` (SPEMi355x)."""
+per-image errors) -- driving any object with ``predict(images) -> (pose, latency_ms)`` (SPEMi355x).
+
+Keypoint mode with MODEL.HEAD.KEYPOINTS_REFINE_ITERS > 0 (``SPEMi355x(..., keypoint_refine=config.keypoint_refine(cfg))``)
+scores the pose refined behind EPnP in both loops: ``predict`` returns it, and ``eval_pipeline`` configures every slot
+of the device loop's ``StreamPipeline`` with it."""
 from __future__ import annotations
 
 from typing import Any, Dict, Iterable, Tuple
