@@ -222,6 +222,55 @@ int spef_score_finalize(spef_score* score, double* stats, void* stream);
 int spef_score_log(spef_score* score, int track, int group, int first, int n, float* rows, int* flags, void* stream);
 int spef_score_destroy(spef_score* score);
 
+/* Pose tracking for video (opt-in; nothing calls it unless asked): an error-state Kalman filter per video stream over the
+ * per-frame pose of any head (spef_decode's, spef_decode_keypoints' or spef_refine_keypoints' outputs), on the device
+ * (Tracking path; spef_amd/spe/track.py is the NumPy twin and states every step).
+ *
+ * State per stream: unit quaternion q (scalar first), position t, angular rate w [rad / frame] (a left perturbation in
+ * the camera frame, R_{k+1} = exp([w]x) R_k: the convention of spef_refine_keypoints, whose cov is a measurement
+ * covariance as it stands), velocity v [m / frame] and the 12 x 12 covariance P of the error state (theta, t, w, v).
+ * One step is one frame: constant velocity, P- = F P F^T + Q with F = [[I6, I6], [0, I6]] (small rotations between
+ * frames). All arithmetic is fp64; the state stays on the device as fp64, so results do not depend on how a sequence
+ * is cut into calls, nor on the number of streams.
+ *
+ * spef_track_params: q[4] process variances added per frame to the (theta, t, w, v) blocks; p0[4] the initial
+ *   variances of the blocks; r[2] the measurement variances (theta, t) of a row without a usable covariance; cov_scale
+ *   multiplies a supplied covariance; gate_chi2 gates on the Mahalanobis distance d2 = y^T S^-1 y (0 = no gate);
+ *   max_coast: a gated row that would be coasted frame number max_coast + 1 in a row starts the track again instead.
+ * spef_track_create: n_streams in 1..65536, every parameter finite and >= 0 (SPEF_ERR_ARG otherwise); all streams start
+ *   without a track. The context is used for its device and its profiler only.
+ * spef_track_step: T time steps of all S streams, time-major (row t * S + s; S must equal n_streams, T >= 1;
+ *   SPEF_ERR_ARG otherwise or for a null required pointer, with nothing enqueued).
+ *   quat [T*S x 4] / pos [T*S x 3]  the measured poses; cov (or NULL) [T*S x 36] their row-major 6 x 6 covariances, order
+ *     (w_x, w_y, w_z, t_x, t_y, t_z), symmetrised; a row with a non-finite entry uses r. status (or NULL) [T*S] the
+ *     decode status: a row with any of bits 1 | 2 | 4 | 8 is an invalid measurement (16 and 32 are informational), as is
+ *     one with a non-finite or zero quaternion, a non-finite position or an S = P-[0:6, 0:6] + R that is not positive
+ *     definite.
+ *   quat_out / pos_out  the tracked pose (they may alias quat / pos); the quaternion is unit and keeps the hemisphere of
+ *     the stream's previous one. d2 (or NULL) [T*S] the Mahalanobis distance (0 on the row that starts a track, NaN
+ *     when none was computed). cov_out (or NULL) [T*S x 36] the pose block P[0:6, 0:6]; rates_out (or NULL)
+ *     [T*S x 6] (w, v).
+ *   track_status [T*S] (a word of its own, not the decode status): 1 = measurement invalid, the row is the prediction;
+ *     2 = gated, likewise; 4 = the track was started again from this row (with 2); 8 = no track and no valid measurement
+ *     to start one: the row passes through unchanged (with 1; d2, cov_out and rates_out are NaN).
+ *   One wave per stream; no atomics, no allocation and no host synchronisation: it can follow the decode on a stream and
+ *   be stream-captured.
+ * spef_track_reset: forget the track of one stream (all streams: -1). spef_track_get_state / spef_track_set_state:
+ *   copy the state of streams [first_stream, first_stream + n) to / from a device buffer of n *
+ *   SPEF_TRACK_STATE_DOUBLES doubles: have (0 / 1), consecutive coasted frames, 0, q[4], t[3], w[3], v[3], P[144]
+ *   row-major. SPEF_ERR_ARG for a stream index out of range. All three are enqueued; no host synchronisation. */
+typedef struct spef_track spef_track;
+typedef struct { double q[4], p0[4], r[2], cov_scale, gate_chi2; int max_coast; } spef_track_params;
+#define SPEF_TRACK_STATE_DOUBLES 160   /* have, coast, 0, q[4], t[3], w[3], v[3], P[144] row-major */
+int spef_track_create(spef_ctx* ctx, int n_streams, const spef_track_params* params, spef_track** out);
+int spef_track_reset(spef_track* track, int stream, void* stream_hip);
+int spef_track_get_state(spef_track* track, int first_stream, int n, double* out_device, void* stream_hip);
+int spef_track_set_state(spef_track* track, int first_stream, int n, const double* in_device, void* stream_hip);
+int spef_track_step(spef_track* track, const float* quat, const float* pos, const float* cov, const int* status,
+                    int T, int S, float* quat_out, float* pos_out, float* d2, float* cov_out, float* rates_out,
+                    int* track_status, void* stream_hip);
+int spef_track_destroy(spef_track* track);
+
 /* Histogram observers for the INT8 calibration: the statistic of every activation-quantizer input of the float model,
  * accumulated on the device over as many frames as the caller streams (Calibration path;
  * spef_amd.quant.observe_host is the NumPy twin and scales_from_stats turns the counts into scales).

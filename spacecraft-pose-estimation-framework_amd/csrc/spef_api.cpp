@@ -1888,6 +1888,112 @@ int spef_score_log(spef_score* sc, int track, int group, int first, int n, float
   return SPEF_OK;
 }
 
+// ------------------------------------------------------------------------------------------ pose tracking
+static_assert(SPEF_TRACK_STATE_DOUBLES == TRACK_STATE, "SPEF_TRACK_STATE_DOUBLES and spef::TRACK_STATE must agree");
+
+struct spef_track {
+  spef_ctx* ctx = nullptr;   // profiler of the step launches
+  int device = 0;
+  int S = 0;
+  TrackParams prm{};
+  double* state = nullptr;   // [S][TRACK_STATE]
+};
+
+int spef_track_destroy(spef_track* tr) {
+  if (!tr) return SPEF_OK;
+  Dev d(tr->device);   // not through ctx: the context may be gone already
+  if (tr->state) hipFree(tr->state);
+  delete tr;
+  return SPEF_OK;
+}
+
+int spef_track_create(spef_ctx* c, int n_streams, const spef_track_params* p, spef_track** out) {
+  if (!c || !p || !out) return fail(SPEF_ERR_ARG, "null argument");
+  if (n_streams < 1 || n_streams > 65536) return fail(SPEF_ERR_ARG, "n_streams must be in 1..65536");
+  bool good = std::isfinite(p->cov_scale) && p->cov_scale >= 0 && std::isfinite(p->gate_chi2) && p->gate_chi2 >= 0 &&
+              p->max_coast >= 0;
+  for (int k = 0; k < 4; ++k)
+    good = good && std::isfinite(p->q[k]) && p->q[k] >= 0 && std::isfinite(p->p0[k]) && p->p0[k] >= 0;
+  for (int k = 0; k < 2; ++k) good = good && std::isfinite(p->r[k]) && p->r[k] >= 0;
+  if (!good) return fail(SPEF_ERR_ARG, "tracker parameters must be finite and not negative");
+  Dev d(c->device);
+  spef_track* tr = new spef_track;
+  tr->ctx = c;
+  tr->device = c->device;
+  tr->S = n_streams;
+  for (int k = 0; k < 4; ++k) {
+    tr->prm.q[k] = p->q[k];
+    tr->prm.p0[k] = p->p0[k];
+  }
+  tr->prm.r[0] = p->r[0];
+  tr->prm.r[1] = p->r[1];
+  tr->prm.cov_scale = p->cov_scale;
+  tr->prm.gate_chi2 = p->gate_chi2;
+  tr->prm.max_coast = (double)p->max_coast;
+  const size_t bytes = (size_t)n_streams * TRACK_STATE * sizeof(double);
+  hipError_t e = hipMalloc(&tr->state, bytes);
+  if (e == hipSuccess) e = hipMemset(tr->state, 0, bytes);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    spef_track_destroy(tr);
+    return fail(SPEF_ERR_HIP, std::string("spef_track_create: ") + hipGetErrorString(e));
+  }
+  *out = tr;
+  return SPEF_OK;
+}
+
+int spef_track_reset(spef_track* tr, int stream, void* stream_hip) {
+  if (!tr) return fail(SPEF_ERR_ARG, "null tracker");
+  if (stream < -1 || stream >= tr->S) return fail(SPEF_ERR_ARG, "stream index out of range");
+  Dev d(tr->device);
+  double* at = tr->state + (stream < 0 ? 0 : (size_t)stream * TRACK_STATE);
+  HIP_TRY(launch_track_reset(at, (int64_t)(stream < 0 ? tr->S : 1) * TRACK_STATE, (hipStream_t)stream_hip));
+  return SPEF_OK;
+}
+
+int spef_track_get_state(spef_track* tr, int first_stream, int n, double* out_device, void* stream_hip) {
+  if (!tr || !out_device) return fail(SPEF_ERR_ARG, "null argument");
+  if (first_stream < 0 || n < 1 || (int64_t)first_stream + n > tr->S)
+    return fail(SPEF_ERR_ARG, "stream index out of range");
+  Dev d(tr->device);
+  HIP_TRY(launch_track_copy(out_device, tr->state + (size_t)first_stream * TRACK_STATE, (int64_t)n * TRACK_STATE,
+                            (hipStream_t)stream_hip));
+  return SPEF_OK;
+}
+
+int spef_track_set_state(spef_track* tr, int first_stream, int n, const double* in_device, void* stream_hip) {
+  if (!tr || !in_device) return fail(SPEF_ERR_ARG, "null argument");
+  if (first_stream < 0 || n < 1 || (int64_t)first_stream + n > tr->S)
+    return fail(SPEF_ERR_ARG, "stream index out of range");
+  Dev d(tr->device);
+  HIP_TRY(launch_track_copy(tr->state + (size_t)first_stream * TRACK_STATE, in_device, (int64_t)n * TRACK_STATE,
+                            (hipStream_t)stream_hip));
+  return SPEF_OK;
+}
+
+int spef_track_step(spef_track* tr, const float* quat, const float* pos, const float* cov, const int* status, int T,
+                    int S, float* quat_out, float* pos_out, float* d2, float* cov_out, float* rates_out,
+                    int* track_status, void* stream_hip) {
+  if (!tr) return fail(SPEF_ERR_ARG, "null tracker");
+  if (!quat || !pos || !quat_out || !pos_out || !track_status) return fail(SPEF_ERR_ARG, "null argument");
+  if (S != tr->S)
+    return fail(SPEF_ERR_ARG, "S = " + std::to_string(S) + ", the tracker has " + std::to_string(tr->S) + " streams");
+  if (T < 1) return fail(SPEF_ERR_ARG, "T must be at least 1");
+  if ((int64_t)T * S * 36 > 0x7fffffff) return fail(SPEF_ERR_ARG, "too many rows");
+  spef_ctx* c = tr->ctx;
+  Dev d(tr->device);
+  hipStream_t s = (hipStream_t)stream_hip;
+  const double rows = (double)T * S;
+  HIP_TRY(prof_launch(c, s, "track_step_kernel",
+                      rows * (2 * 28 + 8 + (cov ? 144 : 0) + (status ? 4 : 0) + (cov_out ? 144 : 0) + (rates_out ? 24 : 0)) +
+                          2.0 * S * TRACK_STATE * 8,
+                      rows * 2.0 * 3000.0, [&] {
+    return launch_track_step(tr->prm, tr->state, quat, pos, cov, status, T, S, quat_out, pos_out, d2, cov_out,
+                             rates_out, track_status, s);
+  }));
+  return SPEF_OK;
+}
+
 int spef_set_keypoints(spef_ctx* c, const float* kp3d, int n, const double* K, float nu, float nv) {
   if (!c || !kp3d || !K || n < 4 || n > 16) return fail(SPEF_ERR_ARG, "bad keypoint configuration");
   Dev d(c->device);

@@ -225,6 +225,20 @@ hipError_t launch_score_finalize(const ScoreLog& lg, int n_tracks, float* scratc
 hipError_t launch_score_read(const ScoreLog& lg, int track, int group, int first, int n, float* rows, int* flags,
                              hipStream_t s);
 
+// ---- pose tracking (k_track.hip; the arithmetic is stated in spef_amd/spe/track.py) ----
+constexpr int TRACK_STATE = 160;   // doubles per stream: have, coast, 0, q[4], t[3], w[3], v[3], P[144] row-major
+struct TrackParams {
+  double q[4], p0[4], r[2], cov_scale, gate_chi2, max_coast;
+};
+// T time steps of S streams, time-major rows (row t * S + s): one wave per stream. cov [T*S][36], status [T*S], d2,
+// cov_out [T*S][36] and rates_out [T*S][6] may be null; quat_out / pos_out may alias quat / pos.
+hipError_t launch_track_step(const TrackParams& p, double* state, const float* quat, const float* pos,
+                             const float* cov, const int* status, int T, int S, float* quat_out, float* pos_out,
+                             float* d2, float* cov_out, float* rates_out, int* track_status, hipStream_t s);
+// Zero n doubles at state (a stream without a track); copy n doubles (get / set state).
+hipError_t launch_track_reset(double* state, int64_t n, hipStream_t s);
+hipError_t launch_track_copy(double* dst, const double* src, int64_t n, hipStream_t s);
+
 // ---- histogram observers of the INT8 calibration (k_observe.hip) ----
 constexpr int OBS_BINS = 8192, OBS_COUNTERS = 8;   // one tap's record: OBS_COUNTERS + OBS_BINS uint64
 // Add the statistic of n values at x (float32, 4-byte aligned; u8: uint8 pixels, value = u / 255) to the record `tap`,

@@ -51,6 +51,12 @@ SIGNATURES = {
     'spef_score_finalize': (_i, [_vp, _vp, _vp]),
     'spef_score_log': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'spef_score_destroy': (_i, [_vp]),
+    'spef_track_create': (_i, [_vp, _i, _vp, C.POINTER(_vp)]),
+    'spef_track_reset': (_i, [_vp, _i, _vp]),
+    'spef_track_get_state': (_i, [_vp, _i, _i, _vp, _vp]),
+    'spef_track_set_state': (_i, [_vp, _i, _i, _vp, _vp]),
+    'spef_track_step': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'spef_track_destroy': (_i, [_vp]),
     'spef_observer_create': (_i, [_vp, C.POINTER(_vp)]),
     'spef_observer_info': (_i, [_vp, _ip, _ip]),
     'spef_observer_reset': (_i, [_vp, _vp]),
@@ -74,6 +80,14 @@ SIGNATURES = {
     'spef_measure_peaks': (_i, [_i, _i, C.POINTER(C.c_double)]),
     'spef_clock_stamp': (_i, [_vp, _i, _vp]),
 }
+
+
+class TrackParams(C.Structure):   # spef_track_params
+    _fields_ = [('q', C.c_double * 4), ('p0', C.c_double * 4), ('r', C.c_double * 2), ('cov_scale', C.c_double),
+                ('gate_chi2', C.c_double), ('max_coast', C.c_int)]
+
+
+TRACK_STATE_DOUBLES = 160
 
 
 class SpefError(RuntimeError):

@@ -196,6 +196,104 @@ class PoseScorer:
             pass
 
 
+class PoseTracker:
+    """Device state of the pose tracker for ``n_streams`` video streams (``Engine.tracker``; csrc/k_track.hip, every
+    step is stated in ``spef_amd.spe.track``): an error-state Kalman filter over the per-frame pose of any head, with
+    Mahalanobis gating and coasting over frames whose decode failed.
+
+    Rows are time-major like the video path's: a batch of ``T * n_streams`` rows holds T consecutive time steps of
+    every stream, row ``t * n_streams + s`` = step t of stream s. ``step`` only enqueues one kernel on the current
+    stream (no allocation in the library, no host sync), so it can follow ``Engine.decode`` /
+    ``Engine.decode_keypoints`` and be captured in a HIP graph.
+
+    Parameters (``spe.track.DEFAULTS``): ``q`` / ``p0`` process and initial variances of the (theta, t, w, v) blocks,
+    ``r`` the fixed measurement variances (theta, t), ``cov_scale``, ``gate_chi2`` (0 = no gate), ``max_coast``. The
+    defaults are the constants of the reference's position filter (q = p0 = 1, r = 100; kalman.py), not tuned values:
+    a deployment sets them for its own frame rate and noise."""
+
+    def __init__(self, engine: 'Engine', n_streams: int, **params):
+        from .spe import track as TK
+        self.engine = engine
+        self.lib = engine.lib
+        self.device = engine.device
+        self.n_streams = int(n_streams)
+        q, p0, r, cov_scale, gate_chi2, max_coast = TK.check_params(**params)
+        self.params = dict(q=tuple(q), p0=tuple(p0), r=tuple(r), cov_scale=cov_scale, gate_chi2=gate_chi2,
+                           max_coast=max_coast)
+        prm = L.TrackParams((C.c_double * 4)(*q), (C.c_double * 4)(*p0), (C.c_double * 2)(*r), cov_scale, gate_chi2,
+                            max_coast)
+        h = C.c_void_p()
+        L.check(self.lib.spef_track_create(engine.ctx, self.n_streams, C.byref(prm), C.byref(h)))
+        self.handle = h
+        self.last_event = None   # StreamPipeline: the event after the last step it enqueued (steps serialise)
+
+    def step(self, dec: dict, T: int, engine: Optional['Engine'] = None, want_cov: bool = False,
+             want_rates: bool = False) -> dict:
+        """``dec``: a decode dict of ``T * n_streams`` time-major rows: 'ori', 'pos', and when present 'status' (the
+        decode status: rows with any of bits 1 | 2 | 4 | 8 are coasted over) and 'cov' ([B x 6 x 6], the pose
+        covariance of ``decode_keypoints(want_cov=True)``). -> {'ori', 'pos', 'mahalanobis', 'track_status'} and, when
+        asked for, 'cov' [B x 6 x 6] (the pose block of P) and 'rates' [B x 6] (w, v) -- device tensors; the inputs are
+        left as they are. ``engine`` is accepted for symmetry with ``VideoFilter.step``; the tracker needs no
+        tables."""
+        quat, pos, status, cov = dec['ori'], dec['pos'], dec.get('status'), dec.get('cov')
+        B, S, dev = quat.shape[0], self.n_streams, self.device
+        assert T >= 1 and B == T * S, f'{B} rows are not T = {T} steps of {S} streams'
+        assert quat.shape == (B, 4) and pos.shape == (B, 3)
+        for t in (quat, pos):
+            assert t.device == dev and t.is_contiguous() and t.dtype == torch.float32
+        if status is not None:
+            assert status.device == dev and status.dtype == torch.int32 and status.numel() == B
+            status = status.contiguous()
+        if cov is not None:
+            assert cov.device == dev and cov.dtype == torch.float32 and cov.numel() == B * 36 and cov.is_contiguous()
+        qo = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        po = torch.empty((B, 3), dtype=torch.float32, device=dev)
+        d2 = torch.empty((B,), dtype=torch.float32, device=dev)
+        ts = torch.empty((B,), dtype=torch.int32, device=dev)
+        co = torch.empty((B, 6, 6), dtype=torch.float32, device=dev) if want_cov else None
+        ro = torch.empty((B, 6), dtype=torch.float32, device=dev) if want_rates else None
+        L.check(self.lib.spef_track_step(self.handle, _ptr(quat), _ptr(pos), _ptr(cov), _ptr(status), T, S, _ptr(qo),
+                                         _ptr(po), _ptr(d2), _ptr(co), _ptr(ro), _ptr(ts), _stream(dev)))
+        out = {'ori': qo, 'pos': po, 'mahalanobis': d2, 'track_status': ts}
+        if want_cov:
+            out['cov'] = co
+        if want_rates:
+            out['rates'] = ro
+        return out
+
+    def reset(self, stream: Optional[int] = None) -> None:
+        """Forget one stream's track (all streams: None); enqueued on the current stream."""
+        L.check(self.lib.spef_track_reset(self.handle, -1 if stream is None else int(stream), _stream(self.device)))
+
+    def state(self, first: int = 0, n: Optional[int] = None) -> torch.Tensor:
+        """The state of streams [first, first + n) as a float64 device tensor [n, 160]: have, consecutive coasted
+        frames, 0, q[4], t[3], w[3], v[3], P[144] row-major (enqueued on the current stream)."""
+        n = self.n_streams - first if n is None else int(n)
+        out = torch.empty((max(n, 0), L.TRACK_STATE_DOUBLES), dtype=torch.float64, device=self.device)
+        L.check(self.lib.spef_track_get_state(self.handle, int(first), n, _ptr(out), _stream(self.device)))
+        return out
+
+    def set_state(self, state, first: int = 0) -> None:
+        """Load the state of streams [first, first + rows) from what ``state`` returned (tensor or array)."""
+        if not isinstance(state, torch.Tensor):
+            state = torch.from_numpy(np.array(state, dtype=np.float64, order='C'))
+        st = state.to(self.device, torch.float64).reshape(-1, L.TRACK_STATE_DOUBLES).contiguous()
+        L.check(self.lib.spef_track_set_state(self.handle, int(first), st.shape[0], _ptr(st), _stream(self.device)))
+        st.record_stream(torch.cuda.current_stream(self.device))
+
+    def close(self) -> None:
+        if getattr(self, 'handle', None):
+            torch.cuda.synchronize(self.device)
+            self.lib.spef_track_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ActivationObserver:
     """Histogram observers behind every activation-quantizer input of the float model (``Engine.observer``;
     csrc/k_observe.hip, the statistic is stated in ``spef_amd.quant.observe_host``): one record of 8 counters and
@@ -415,6 +513,12 @@ class Engine:
         ``capacity`` rows per (group, track), at most 2^20."""
         return PoseScorer(self, n_groups, n_tracks, capacity)
 
+    def tracker(self, n_streams: int, **params) -> 'PoseTracker':
+        """The pose tracker (an error-state Kalman filter with gating and coasting) for ``n_streams`` independent
+        video streams on this engine's device; works behind every head. ``params``: q, p0, r, cov_scale, gate_chi2,
+        max_coast (``PoseTracker``; the defaults are the reference filter's constants, not tuned)."""
+        return PoseTracker(self, n_streams, **params)
+
     def observer(self) -> 'ActivationObserver':
         """Histogram observers for the INT8 calibration (``quant.calibrate_device``): one tap per activation
         quantizer of the loaded model. ``observe`` needs an fp32 blob in this engine."""
@@ -441,7 +545,9 @@ class Engine:
         self.epoch += 1
         self._kp = (kp, kk, dd)
 
-    def decode_keypoints(self, raw: torch.Tensor, apply_sigmoid: bool = True):
+    def decode_keypoints(self, raw: torch.Tensor, apply_sigmoid: bool = True, want_cov: bool = False):
+        """``want_cov``: with the refinement on (``set_keypoint_refine``), add 'cov' [B x 6 x 6], the refined pose's
+        covariance (what ``PoseTracker.step`` takes as the measurement covariance). Off by default."""
         B = raw.shape[0]
         dev = self.device
         kp = torch.empty_like(raw)
@@ -453,9 +559,12 @@ class Engine:
         dec = {'keypoints': kp, 'ori': quat, 'pos': pos, 'status': status}
         refine = self._kp_refine
         if refine is not None:   # set_keypoint_refine: Levenberg-Marquardt behind EPnP, same stream
-            ref = self.refine_keypoints(kp, quat, pos, max_iters=refine[0], huber_px=refine[1], status=status)
+            ref = self.refine_keypoints(kp, quat, pos, max_iters=refine[0], huber_px=refine[1], status=status,
+                                        want_cov=want_cov)
             dec.update(ori=ref['ori'], pos=ref['pos'], ori_epnp=quat, pos_epnp=pos, fit=ref['fit'],
                        refine_iters=ref['iters'])
+            if want_cov:
+                dec['cov'] = ref['cov']
         return dec
 
     def set_keypoint_refine(self, max_iters=None, huber_px: float = 0.0) -> None:

@@ -14,6 +14,11 @@ previous still frame (:136-144), keypoints / bounding box for visualisation (:14
 
 ``predict_sequence`` is the same loop for T consecutive frames of one video in one call: one batched forward, one
 decode and one video-filter step on the device (csrc/k_video.hip), sharing its state with ``predict``.
+
+``video_type='Tracker'`` (both calls; not in the reference, which ships a Kalman filter it never wires in) tracks the
+pose of any head, keypoint mode included, with the device tracker (csrc/k_track.hip, ``Engine.tracker``):
+``pose_video`` = {'ori', 'pos', 'mahalanobis', 'track_status', 'keypoints', 'bbox'}. Its parameters are
+``Inference.tracker_params``; its state lives on the device and ``reset()`` clears it.
 """
 from __future__ import annotations
 
@@ -55,6 +60,7 @@ class Inference:
         self.prev_video_ori = None
         self.pdf_adapt_ori = TemporalPDF(n=0.8, alpha=16.49, distance_metric='l2')    # inference.py:38-39
         self.pdf_adapt_pos = TemporalPDF(n=0.5, alpha=48.64, distance_metric='l2')
+        self.tracker_params = {}     # video_type 'Tracker': the parameters of Engine.tracker (q, p0, r, gate_chi2, ...)
         self.img_size = None
         self.device = device
         self.dtype = dtype
@@ -84,6 +90,9 @@ class Inference:
         self.prev_video_ori = None
         self.pdf_adapt_ori.reset()
         self.pdf_adapt_pos.reset()
+        eng = self.inference_engine
+        if getattr(eng, '_track', None) is not None:     # video_type 'Tracker': the state lives on the device
+            eng._track[1].reset()
 
     def update(self, model, spe_utils) -> None:
         """inference.py:103-115."""
@@ -118,6 +127,44 @@ class Inference:
             raise ValueError('Weighted PDF contains NaN or sums to zero')   # classification_utils.py:134-135, 253
         return dec['ori'][0].cpu().numpy(), dec['pos'][0].cpu().numpy()
 
+    def _still_pole(self, ori: np.ndarray) -> np.ndarray:
+        """The pole rule of ``predict`` over a run of still quaternions [T x 4], on the host -> the run, flipped."""
+        ori = np.array(ori, copy=True)
+        for t in range(ori.shape[0]):
+            if self.prev_still_ori is None:
+                self.prev_still_ori = ori[t]
+                continue
+            dot = np.dot(self.prev_still_ori, ori[t])
+            if dot < 0:
+                ori[t] = -ori[t]
+            if np.abs(dot) > 0.5:
+                self.prev_still_ori = ori[t]
+        return ori
+
+    def _tracked(self, images: torch.Tensor) -> list:
+        """video_type 'Tracker' for T consecutive frames of one video: one batched forward, one decode and one
+        tracker step on the GPU (``SPEMi355x.predict_tracked``, one stream; the state stays in the device tracker, so
+        any cut of a video into calls gives the same poses). -> T triples (pose_still, latency_ms, pose_video) with
+        pose_video = {'ori', 'pos', 'mahalanobis', 'track_status', 'keypoints', 'bbox'}; in keypoint mode its
+        'keypoints' are the reprojection of the tracked pose."""
+        eng, su = self.inference_engine, self.spe_utils
+        if not hasattr(eng, 'predict_tracked'):
+            raise ValueError("video filtering 'Tracker' needs the 'gpu_mi355x' engine")
+        T = int(images.shape[0])
+        still, tracked, latency_ms = eng.predict_tracked(images, 1, **self.tracker_params)
+        still = dict(still)
+        still['ori'] = self._still_pole(still['ori'])
+        out = []
+        for t in range(T):
+            pose_still = {k: v[t] for k, v in still.items()}
+            self._visual(pose_still)
+            pose_video = {k: v[t] for k, v in tracked.items()}
+            if su.keypoints is not None:
+                pose_video['keypoints'] = su.keypoints.create_keypoints2d(pose_video['ori'], pose_video['pos'])
+                pose_video['bbox'] = su.keypoints.create_bbox_from_keypoints(pose_video['keypoints'])
+            out.append((pose_still, latency_ms / T, pose_video))
+        return out
+
     @staticmethod
     def _advance_pole(pole, quats: np.ndarray):
         """The pole after a run of quaternions that already follow it (the rule of ``predict``; no flips left)."""
@@ -135,6 +182,9 @@ class Inference:
         step and read back after it, so ``reset()`` clears both and the two calls can be mixed on one video.
         An engine without ``predict_video`` (one of the reference's own, through ``engine_factories``) is driven
         frame by frame."""
+        if video_type == 'Tracker':
+            self.img_size = (1,) + tuple(images.size())[1:]
+            return self._tracked(images)
         if video_type is not None and video_type != 'Adaptative':
             raise ValueError(f'type of video filtering not implemented: {video_type}')
         eng = self.inference_engine
@@ -186,6 +236,8 @@ class Inference:
         """inference.py:117-191: -> (pose of the still frame, latency ms, filtered video pose or None)."""
         if not self.img_size or self.img_size != tuple(image.size()):
             self.img_size = tuple(image.size())
+        if video_type == 'Tracker':      # the pose tracker (any head): still and tracked pose from one device pass
+            return self._tracked(image)[0]
         pose_still, latency_ms = self.inference_engine.predict(image)
         pose_still = {k: v.squeeze(0) for k, v in pose_still.items()}
         if self.prev_still_ori is not None:   # no quaternion sign flips between frames

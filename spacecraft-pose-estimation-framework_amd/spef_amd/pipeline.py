@@ -62,7 +62,7 @@ class StreamPipeline:
             e.reserve(B, H, W)
 
     def submit(self, frames: torch.Tensor, ori_mode: int = L.CLASSIFICATION, pos_mode: int = L.REGRESSION,
-               want_soft: bool = True, video=None, score=None) -> dict:
+               want_soft: bool = True, video=None, score=None, track=None) -> dict:
         """Enqueue forward + decode of one batch on the next stream; returns the decode dict (device tensors,
         valid once that stream reaches them -- ``synchronize()`` or the dict's 'event').
 
@@ -76,7 +76,13 @@ class StreamPipeline:
         time-major, and the batch's true poses ({'ori', 'pos'}; device tensors, or host arrays that are copied).
         The scoring step is enqueued on the slot's stream after the decode (and after the video step: track 0 then
         logs the still poses, track 1 the filtered ones), outside the recorded graph, and ordered after the previous
-        submit's scoring step by an event exactly as the video steps are."""
+        submit's scoring step by an event exactly as the video steps are.
+
+        ``track``: a ``PoseTracker`` (``Engine.tracker``) whose streams this batch holds, time-major; any head. Its
+        step is enqueued on the slot's stream after the decode, outside the recorded graph, and ordered after the
+        previous submit's step through ``track.last_event`` exactly as ``video=`` is. The result is the dict's
+        'track' entry (``PoseTracker.step``); with ``score`` as well, track 1 logs the tracked poses (flagged only
+        where a row passed through without a track)."""
         i = self._next
         self._next = (i + 1) % self.depth
         eng, s = self.engines[i], self.streams[i]
@@ -111,9 +117,31 @@ class StreamPipeline:
                 ev = torch.cuda.Event()
                 ev.record(s)
             video.last_event = dec['event'] = ev
+        if track is not None:
+            assert video is None, 'one batch goes through the video filter or the tracker, not both'
+            self._track(s, dec, track, eng)
         if score is not None:
-            self._score(s, dec, score, dec.get('video'))
+            self._score(s, dec, score, dec.get('video') or self._tracked_for_score(s, dec))
         return dec
+
+    def _track(self, s, dec: dict, track, eng) -> None:
+        B = dec['ori'].shape[0]
+        assert B % track.n_streams == 0, f'{B} frames are not whole time steps of {track.n_streams} streams'
+        with torch.cuda.stream(s):
+            if track.last_event is not None:
+                s.wait_event(track.last_event)           # the tracker's state: steps in submit order
+            dec['track'] = track.step(dec, B // track.n_streams, engine=eng)
+            ev = torch.cuda.Event()
+            ev.record(s)
+        track.last_event = dec['event'] = ev
+
+    @staticmethod
+    def _tracked_for_score(s, dec: dict):
+        """The tracked poses as the scorer takes them: a row counts as failed only where it passed through."""
+        if 'track' not in dec:
+            return None
+        with torch.cuda.stream(s):
+            return dict(dec['track'], status=dec['track']['track_status'] & 8)
 
     def _score(self, s, dec: dict, score, video_dec=None) -> None:
         scorer, targets = score
@@ -175,10 +203,11 @@ class StreamPipeline:
         for e in self.engines:
             e.set_keypoint_refine(max_iters, huber_px)
 
-    def submit_keypoints(self, frames: torch.Tensor, score=None) -> dict:
+    def submit_keypoints(self, frames: torch.Tensor, score=None, track=None) -> dict:
         """Keypoint mode: forward (KeypointRegressionHead) + sigmoid + batched EPnP (+ the pose refinement, when
         ``set_keypoint_refine`` turned it on) of one batch on the next stream; returns the decode dict of
-        Engine.decode_keypoints plus 'raw' and 'event' (as submit()). ``score``: as in ``submit``."""
+        Engine.decode_keypoints plus 'raw' and 'event' (as submit()). ``score``, ``track``: as in ``submit``; with
+        the refinement on, the tracker gets the refined pose's covariance (the dict then has 'cov')."""
         i = self._next
         self._next = (i + 1) % self.depth
         eng, s = self.engines[i], self.streams[i]
@@ -186,17 +215,19 @@ class StreamPipeline:
         with torch.cuda.stream(s):
             frames.record_stream(s)
             raw, _ = eng.forward(frames)   # allocated on s: every returned tensor belongs to this batch alone
-            dec = eng.decode_keypoints(raw)
+            dec = eng.decode_keypoints(raw, want_cov=track is not None)
             ev = torch.cuda.Event()
             ev.record(s)
         dec['raw'] = raw
         dec['event'] = ev
+        if track is not None:
+            self._track(s, dec, track, eng)
         if score is not None:
             scored = dec
             if 'ori_epnp' in dec:   # the refinement's bits 16 / 32 are informational, not decode failures
                 with torch.cuda.stream(s):
                     scored = dict(dec, status=dec['status'] & 15)
-            self._score(s, scored, score)
+            self._score(s, scored, score, self._tracked_for_score(s, dec))
             dec['event'] = scored['event']
         return dec
 

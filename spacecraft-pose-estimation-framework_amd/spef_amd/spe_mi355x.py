@@ -46,6 +46,7 @@ class SPEMi355x:
         self.device = torch.device(device)
         self.engine = None
         self._video = None          # (configuration, VideoFilter) of predict_video
+        self._track = None          # (configuration, PoseTracker) of predict_tracked
         self._pipe = None           # StreamPipeline of evaluation_device
         self.update_model(model, self.device)
 
@@ -91,6 +92,7 @@ class SPEMi355x:
 
     def delete_model(self) -> None:
         self._close_video()
+        self._close_track()
         self._close_pipe()
         if self.engine is not None:
             self.engine.close()
@@ -215,8 +217,62 @@ class SPEMi355x:
                                                    'pos_distance')}
         return still, video, start.elapsed_time(end)
 
-    def _pose(self, dec) -> Dict:
-        status = dec['status'].cpu().numpy()
+    # ------------------------------------------------------------------ tracking
+    def tracker(self, n_streams: int = 1, **params):
+        """The engine's ``PoseTracker`` for this configuration (created on first use, kept with its state until the
+        configuration changes or the model is deleted). ``params``: q, p0, r, cov_scale, gate_chi2, max_coast."""
+        key = (int(n_streams), tuple(sorted((k, tuple(np.atleast_1d(v).tolist())) for k, v in params.items())))
+        if self._track is None or self._track[0] != key:
+            self._close_track()
+            self._track = (key, self.engine.tracker(n_streams, **params))
+        return self._track[1]
+
+    def _close_track(self) -> None:
+        if getattr(self, '_track', None) is not None:
+            self._track[1].close()
+        self._track = None
+
+    def predict_tracked(self, images: torch.Tensor, n_streams: int = 1, targets=None, scorer=None,
+                        **params) -> Tuple[Dict, Dict, float]:
+        """Time-major video frames ``images`` [T * n_streams, ...] (row t * n_streams + s = step t of stream s) ->
+        (still pose, tracked pose, latency ms) for every head mode: one batched forward, one decode and one tracker
+        step (``Engine.tracker``: an error-state Kalman filter with gating and coasting), all on the GPU. The still
+        pose is what ``predict`` returns, except that a row whose decode failed does not raise here: the tracker coasts
+        over it and reports it in ``tracked['track_status']`` (bit 1; with bit 8 when the stream has no track yet and the
+        row passes through). The tracked pose has 'ori', 'pos', 'mahalanobis' and 'track_status'. In keypoint mode with
+        ``keypoint_refine`` the refined pose's covariance is the measurement covariance; otherwise the fixed ``r`` is.
+        The tracker's state persists between calls (``tracker(...).reset()`` starts new videos). ``params``: as
+        ``Engine.tracker``. With ``targets`` and ``scorer`` (``engine.scorer(n_streams, 2, capacity)``) track 0 logs the
+        still poses and track 1 the tracked ones; a tracked row counts as failed only where it passed through."""
+        if self.engine is None:
+            raise AssertionError('no model loaded')
+        x = images.to(self.device, non_blocking=True).contiguous()
+        B = x.shape[0]
+        if n_streams < 1 or B % n_streams:
+            raise AssertionError(f'{B} frames are not whole time steps of {n_streams} streams')
+        trk = self.tracker(n_streams, **params)
+        torch.cuda.synchronize(self.device)
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        raw0, raw1 = self.engine.forward(x)
+        if self.keypoint_mode:
+            dec = self.engine.decode_keypoints(raw0, apply_sigmoid=True, want_cov=self.keypoint_refine is not None)
+        else:
+            dec = self.engine.decode(self.ori_mode, self.pos_mode, raw0, raw1)
+        out = trk.step(dec, B // n_streams)
+        if targets is not None and scorer is not None:
+            if scorer.n_groups != n_streams or scorer.n_tracks < 2:
+                raise AssertionError(f'the scorer needs {n_streams} groups and 2 tracks')
+            tg = scorer.targets(targets)
+            scorer.step(0, dict(dec, status=dec['status'] & 15), tg, B // n_streams)
+            scorer.step(1, dict(out, status=out['track_status'] & 8), tg, B // n_streams)
+        end.record()
+        end.synchronize()
+        tracked = {k: out[k].cpu().numpy() for k in ('ori', 'pos', 'mahalanobis', 'track_status')}
+        return self._pose(dec, check=False), tracked, start.elapsed_time(end)
+
+    def _pose(self, dec, check: bool = True) -> Dict:
+        status = dec['status'].cpu().numpy() if check else np.zeros(1, np.int32)
         if np.any(status & 1):
             raise ValueError('Error during orientation decoding')                       # classification_utils.py:135
         if np.any(status & 2):
