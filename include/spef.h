@@ -307,7 +307,10 @@ int spef_observer_destroy(spef_observer* obs);
 
 /* Keypoint mode (ORI == POS == 'keypoints', config.py:53-58): the 3-D model points (host float32 n x 3,
  * e.g. tangoPoints.mat's 11 Tango keypoints, keypoints_utils.py:31-45), the camera matrix (host float64
- * 3x3 row-major) and the image size the keypoints are normalised by (Camera nu, nv; speed.py:18-32). */
+ * 3x3 row-major) and the image size the keypoints are normalised by (Camera nu, nv; speed.py:18-32).
+ * All or nothing: on any failure (SPEF_ERR_ARG: a null pointer, n outside 4..16, a degenerate -- coplanar -- model;
+ * SPEF_ERR_HIP: an allocation or a copy) the previous configuration stays exactly as it was, and a context that had
+ * none stays unconfigured (spef_decode_keypoints / spef_refine_keypoints return SPEF_ERR_STATE). */
 int spef_set_keypoints(spef_ctx* ctx, const float* kp3d, int n, const double* K, float nu, float nv);
 
 /* Lens distortion of the keypoint camera, OpenCV order (k1, k2, p1, p2[, k3]); n = 0 removes it. The keypoint

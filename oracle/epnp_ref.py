@@ -163,8 +163,9 @@ def control_points_and_alphas(pw):
     return cws, _alphas(pw, cws)
 
 
-def epnp(pw, us, k=SPEED_K):
-    """-> (R 3x3, t 3): pose of the 3-D points pw (n x 3) seen at pixels us (n x 2)."""
+def epnp(pw, us, k=SPEED_K, return_winner=False):
+    """-> (R 3x3, t 3): pose of the 3-D points pw (n x 3) seen at pixels us (n x 2). With ``return_winner`` also the
+    beta approximation (1, 2 or 3) whose pose had the lowest reprojection error."""
     pw = np.asarray(pw, np.float64)
     us = np.asarray(us, np.float64)
     fu, fv, uc, vc = k[0, 0], k[1, 1], k[0, 2], k[1, 2]
@@ -174,26 +175,29 @@ def epnp(pw, us, k=SPEED_K):
     _, _, ut = np.linalg.svd(m.T @ m)                 # rows sorted by descending singular value
     l, rho = _l6x10(ut), _rho(cws)
     best = None
-    for fn in (_betas1, _betas2, _betas3):
+    for ap, fn in enumerate((_betas1, _betas2, _betas3), 1):
         b = _gauss_newton(l, rho, fn(l, rho))
         r, t, err = _r_and_t(ut, b, alphas, pw, us, fu, fv, uc, vc)
         if best is None or err < best[2]:
-            best = (r, t, err)
-    return best[0], best[1]
+            best = (r, t, err, ap)
+    return (best[0], best[1], best[3]) if return_winner else (best[0], best[1])
 
 
-def undistort_points(us32, k, dist=None, iters=5):
+def undistort_points(us32, k, dist=None, iters=5, return_fallback=False):
     """cv::undistortPoints(src, dst, K, D) as solvePnP(SOLVEPNP_EPNP) calls it before EPnP (OpenCV 4.5.5
     calib3d/src/solvepnp.cpp, undistort.dispatch.cpp cvUndistortPointsInternal; default criteria COUNT = 5):
     x = (u - cx) / fx (as a product with 1/fx), then x <- (x0 - delta(x)) * icdist(x) five times (k4..k6 and the thin
     prism / tilt terms are 0 for a 5-coefficient model; icdist < 0 falls back to the distorted point), output
     rounded to the input's float32; epnp::init_points then re-projects with K (us = x * fu + uc, in double).
     With ``dist`` None or all zeros only the float32 round trip of the normalised coordinate remains (the reference
-    passes zeros for SPEED, keypoints_utils.py:136)."""
+    passes zeros for SPEED, keypoints_utils.py:136). With ``return_fallback`` also a bool per point: it took the
+    icdist < 0 fallback."""
     fu, fv, uc, vc = k[0, 0], k[1, 1], k[0, 2], k[1, 2]
     ifx, ify = 1.0 / fu, 1.0 / fv
+    fell = np.zeros(us32.shape[0], bool)
     d = np.zeros(5) if dist is None else np.asarray(dist, np.float64).reshape(-1)
-    k1, k2, p1, p2, k3 = d[:5]
+    assert d.size in (4, 5), 'distCoeffs: (k1, k2, p1, p2) or (k1, k2, p1, p2, k3)'
+    k1, k2, p1, p2, k3 = np.concatenate([d, np.zeros(5 - d.size)])    # the 4-coefficient form has k3 = 0
     out = np.zeros((us32.shape[0], 2))
     for i in range(us32.shape[0]):
         u, v = float(us32[i, 0]), float(us32[i, 1])
@@ -204,6 +208,7 @@ def undistort_points(us32, k, dist=None, iters=5):
             icdist = 1.0 / (1 + ((k3 * r2 + k2) * r2 + k1) * r2)
             if icdist < 0:
                 x, y = (u - uc) * ifx, (v - vc) * ify
+                fell[i] = True
                 break
             dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
             dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
@@ -211,23 +216,30 @@ def undistort_points(us32, k, dist=None, iters=5):
             y = (y0 - dy) * icdist
         out[i, 0] = float(np.float32(x)) * fu + uc
         out[i, 1] = float(np.float32(y)) * fv + vc
-    return out
+    return (out, fell) if return_fallback else out
 
 
-def pnp(kp2d_norm, kp3d, k=SPEED_K, nu=SPEED_NU, nv=SPEED_NV, dist=None):
-    """KeyPoints.pnp (keypoints_utils.py:112-150): normalised (x0,y0,x1,y1,...) incl. origin -> (q f32, t f32)."""
-    x = kp2d_norm[0::2] * nu
-    y = kp2d_norm[1::2] * nv
-    us32 = np.stack([x, y], axis=1)[1:].astype(np.float32)         # float32 pixels (keypoints_utils.py:127-131)
+def pixels_f32(kp2d_norm, nu=SPEED_NU, nv=SPEED_NV):
+    """keypoints_utils.py:127-131: normalised (x0,y0,x1,y1,...) incl. origin -> float32 pixels [n x 2], origin dropped."""
+    return np.stack([kp2d_norm[0::2] * nu, kp2d_norm[1::2] * nv], axis=1)[1:].astype(np.float32)
+
+
+def pnp(kp2d_norm, kp3d, k=SPEED_K, nu=SPEED_NU, nv=SPEED_NV, dist=None, return_winner=False):
+    """KeyPoints.pnp (keypoints_utils.py:112-150): normalised (x0,y0,x1,y1,...) incl. origin -> (q f32, t f32) and,
+    with ``return_winner``, the winning beta approximation (1, 2 or 3)."""
+    us32 = pixels_f32(kp2d_norm, nu, nv)
     us = undistort_points(us32, k, dist)
-    r, t = epnp(np.asarray(kp3d, np.float32).astype(np.float64), us, k)
-    return dcm2quat(r).astype(np.float32), np.asarray(t, np.float32)
+    r, t, win = epnp(np.asarray(kp3d, np.float32).astype(np.float64), us, k, return_winner=True)
+    q, t = dcm2quat(r).astype(np.float32), np.asarray(t, np.float32)
+    return (q, t, win) if return_winner else (q, t)
 
 
-def decode_batch(kp2d_norm, kp3d, k=SPEED_K, nu=SPEED_NU, nv=SPEED_NV, dist=None):
-    """KeyPoints.decode_batch (keypoints_utils.py:152-174)."""
+def decode_batch(kp2d_norm, kp3d, k=SPEED_K, nu=SPEED_NU, nv=SPEED_NV, dist=None, return_winner=False):
+    """KeyPoints.decode_batch (keypoints_utils.py:152-174); with ``return_winner`` also the winning beta approximation
+    of every row (int, 1..3)."""
     q = np.zeros((kp2d_norm.shape[0], 4), np.float32)
     t = np.zeros((kp2d_norm.shape[0], 3), np.float32)
+    win = np.zeros(kp2d_norm.shape[0], np.int64)
     for i in range(kp2d_norm.shape[0]):
-        q[i], t[i] = pnp(kp2d_norm[i], kp3d, k, nu, nv, dist)
-    return q, t
+        q[i], t[i], win[i] = pnp(kp2d_norm[i], kp3d, k, nu, nv, dist, return_winner=True)
+    return (q, t, win) if return_winner else (q, t)

@@ -1996,13 +1996,9 @@ int spef_track_step(spef_track* tr, const float* quat, const float* pos, const f
 
 int spef_set_keypoints(spef_ctx* c, const float* kp3d, int n, const double* K, float nu, float nv) {
   if (!c || !kp3d || !K || n < 4 || n > 16) return fail(SPEF_ERR_ARG, "bad keypoint configuration");
-  Dev d(c->device);
-  if (c->kp3d) hipFree(c->kp3d);
-  if (c->kp_model) hipFree(c->kp_model);
-  c->kp3d = nullptr;
-  c->kp_model = nullptr;
-  HIP_TRY(hipMalloc(&c->kp3d, sizeof(float) * 3 * n));
-  HIP_TRY(hipMemcpy(c->kp3d, kp3d, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+  // All or nothing: the model is computed and checked on the host and both device buffers are allocated and filled
+  // before anything in the context changes, so a failure (a degenerate model, a failed allocation or copy) leaves the
+  // previous configuration -- or none -- exactly as it was.
   // epnp.cpp choose_control_points + compute_barycentric_coordinates depend only on the 3-D model: do them
   // once here (fp64). PCA axis signs are canonical (largest-|component| positive; oracle/epnp_ref.py too).
   std::vector<double> model(12 + 4 * (size_t)n);
@@ -2087,8 +2083,22 @@ int spef_set_keypoints(spef_ctx* c, const float* kp3d, int n, const double* K, f
       model[12 + 4 * i + 3] = al[2];
     }
   }
-  HIP_TRY(hipMalloc(&c->kp_model, sizeof(double) * model.size()));
-  HIP_TRY(hipMemcpy(c->kp_model, model.data(), sizeof(double) * model.size(), hipMemcpyHostToDevice));
+  Dev d(c->device);
+  float* new_kp3d = nullptr;
+  double* new_model = nullptr;
+  hipError_t e = hipMalloc(&new_kp3d, sizeof(float) * 3 * n);
+  if (e == hipSuccess) e = hipMalloc(&new_model, sizeof(double) * model.size());
+  if (e == hipSuccess) e = hipMemcpy(new_kp3d, kp3d, sizeof(float) * 3 * n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(new_model, model.data(), sizeof(double) * model.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (new_kp3d) hipFree(new_kp3d);
+    if (new_model) hipFree(new_model);
+    return fail(SPEF_ERR_HIP, std::string("spef_set_keypoints: ") + hipGetErrorString(e));
+  }
+  if (c->kp3d) hipFree(c->kp3d);
+  if (c->kp_model) hipFree(c->kp_model);
+  c->kp3d = new_kp3d;
+  c->kp_model = new_model;
   c->kp_n = n;
   memcpy(c->camK, K, sizeof(c->camK));
   c->cam_nu = nu;
@@ -2116,7 +2126,7 @@ int spef_set_keypoint_distortion(spef_ctx* c, const double* dist, int n) {
 int spef_decode_keypoints(spef_ctx* c, const float* raw, int B, int apply_sigmoid, float* kp_out, float* quat,
                           float* pos, int* status, void* stream) {
   if (!c || !raw || !quat || !pos || !status || B <= 0) return fail(SPEF_ERR_ARG, "null argument");
-  if (!c->kp3d) return fail(SPEF_ERR_STATE, "keypoints not configured (spef_set_keypoints)");
+  if (!c->kp3d || !c->kp_model) return fail(SPEF_ERR_STATE, "keypoints not configured (spef_set_keypoints)");
   Dev d(c->device);
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipMemsetAsync(status, 0, sizeof(int) * B, s));
@@ -2133,7 +2143,7 @@ int spef_refine_keypoints(spef_ctx* c, const float* kp, const float* weights, in
   if (!c || !kp || !quat_inout || !pos_inout || !status || B <= 0) return fail(SPEF_ERR_ARG, "null argument");
   if (max_iters < 1 || max_iters > 100) return fail(SPEF_ERR_ARG, "max_iters must be in 1..100");
   if (!(huber_px >= 0.0f) || !std::isfinite(huber_px)) return fail(SPEF_ERR_ARG, "huber_px must be finite and >= 0");
-  if (!c->kp3d) return fail(SPEF_ERR_STATE, "keypoints not configured (spef_set_keypoints)");
+  if (!c->kp3d || !c->kp_model) return fail(SPEF_ERR_STATE, "keypoints not configured (spef_set_keypoints)");
   Dev d(c->device);
   hipStream_t s = (hipStream_t)stream;
   const int n = c->kp_n;
