@@ -117,7 +117,9 @@ int spef_decode(spef_ctx* ctx, int ori_mode, int pos_mode, const float* ori_raw,
  *   (the reference's Inference engine: ori 0.8 / 16.49, pos 0.5 / 48.64, L2). The bin counts are those of the
  *   context's decode tables, which must both be set (SPEF_ERR_STATE otherwise; spef_video_step returns
  *   SPEF_ERR_STATE as well when the tables were replaced by ones of other sizes since). An unknown metric or
- *   n_streams < 1: SPEF_ERR_ARG. Every stream starts reset. */
+ *   n_streams < 1: SPEF_ERR_ARG. Every stream starts reset. The filter keeps a stream's PDF in registers, at most
+ *   8192 bins per table: with more in either table (a 21^3 = 9261-bin position grid, which spef_set_decode_tables
+ *   and the still-frame spef_decode accept) spef_video_create returns SPEF_ERR_ARG and leaves *out as it was. */
 enum spef_video_metric {   /* spef_amd.temporal.METRICS order */
   SPEF_METRIC_L2 = 0,
   SPEF_METRIC_KL = 1,

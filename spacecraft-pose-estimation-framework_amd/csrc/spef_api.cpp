@@ -1599,6 +1599,12 @@ int spef_video_create(spef_ctx* c, int n_streams, int metric, float n_ori, float
   if (metric < VM_L2 || metric > VM_WASSERSTEIN) return fail(SPEF_ERR_ARG, "unknown distance metric");
   if (!c->d_ori_bins || !c->d_pos_grid)
     return fail(SPEF_ERR_STATE, "the video filter needs both decode tables (spef_set_decode_tables)");
+  // video_scan_kernel keeps a stream's PDF in registers, at most 32 bins per thread (launch_video_scan has the same
+  // guard): refuse a larger table here, not at every step. The still-frame position decode has no such limit.
+  if (c->n_ori_bins > 8192 || c->n_pos_bins > 8192)
+    return fail(SPEF_ERR_ARG, "the video filter takes at most 8192 bins per table, the " +
+                                  std::string(c->n_ori_bins > 8192 ? "orientation" : "position") + " table has " +
+                                  std::to_string(c->n_ori_bins > 8192 ? c->n_ori_bins : c->n_pos_bins));
   Dev d(c->device);
   spef_video* v = new spef_video;
   v->device = c->device;
