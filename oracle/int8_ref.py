@@ -35,7 +35,8 @@ Integer semantics (every scale a float64 on the host):
                 clip to [0, 255] after ReLU, to [-128, 127] for the signed shared quantizers
   residual      q_sum = q_proj + q_in (both at the block's shared scale s_q), then requantised to the next
                 consumer's scale: clip_s8(fixed(q_sum, s_q / s_next, 0))
-  input         u8 frame -> q = clip(rint(f32(f32(u) / 255) / f32(s_img)), -128, 127) (float32 ops)
+  input         u8 frame -> q = clip(rint(f32(f32(u) / 255) / f32(s_img)), -128, 127) (float32 ops); a float32 NCHW
+                frame x -> q = clip(rint(f32(x) / f32(s_img)), -128, 127), the same operations from the division on
   pool          sum over the H*W map, shifted right by tb = b_last + ceil(log2(H*W)) - b_pool (TruncTo8bit
                 floor; ceil(log2(H*W)) at 8 bits): pooled u8 at scale s_pool = s_l * 2**tb / (H*W)
   FC            q_b[c] = clip(rint(b[c] / (s_pool * s_w[c])), -128, 127); out = f32(acc) * f32(s_pool * s_w[c])
@@ -124,11 +125,14 @@ def fixed(m, b):
     return M, B, S
 
 
-def requant(acc, M, B, S, lo, hi, axis=1):
-    """clip((acc * M + B) >> sh, lo, hi) with per-channel (M, B, sh) along ``axis`` of int64 ``acc``."""
+def requant(acc, M, B, S, lo, hi, axis=1, clipped=None):
+    """clip((acc * M + B) >> sh, lo, hi) with per-channel (M, B, sh) along ``axis`` of int64 ``acc``. ``clipped``: a
+    list that receives (values below lo, values above hi) before the clip."""
     shp = [1] * acc.ndim
     shp[axis] = -1
     v = (acc * M.reshape(shp) + B.reshape(shp)) >> S.reshape(shp)
+    if clipped is not None:
+        clipped.append((int((v < lo).sum()), int((v > hi).sum())))
     return np.clip(v, lo, hi)
 
 
@@ -146,6 +150,15 @@ def input_lut(s_img: float, bits: int = 8) -> np.ndarray:
     the signed input quantizer (QuantIdentity(signed=True), mobilenet_v2.py:177-178)."""
     x = np.arange(256, dtype=np.float32) / np.float32(255.0)
     return np.clip(np.rint(x / np.float32(s_img)), -(1 << (bits - 1)), (1 << (bits - 1)) - 1).astype(np.int64)
+
+
+def input_quant_f32(x, s_img: float, bits: int = 8) -> np.ndarray:
+    """float32 NCHW frames -> quantized input: clip(rint(f32(x) / f32(s_img))) to the signed input quantizer, every
+    operation in float32 -- the arithmetic of ``input_lut`` without its /255, and of the stem kernels' float-frame
+    branch (csrc/k_q8.hip). Values outside [0, 1] are legal and meet the clip on either side."""
+    x = _np(x).astype(np.float32)
+    lo, hi = -(1 << (bits - 1)), (1 << (bits - 1)) - 1
+    return np.clip(np.rint(x / np.float32(s_img)), np.float32(lo), np.float32(hi)).astype(np.int64)
 
 
 def _conv_int(x, q, stride, groups):
@@ -177,14 +190,25 @@ def head_params(sd, qp: Dict, hw: int):
     return tb, out
 
 
-def int8_forward(frames_u8: np.ndarray, sd: Dict, qp: Dict, residual: bool = True, upto: int | None = None):
-    """uint8 NHWC frames -> (ori logits f32, pos f32), or the integer activation after block ``upto``
-    (NCHW int64; 0 = stem output) / ``upto='last'`` (last conv output) / ``upto='pool'``."""
+def int8_forward(frames_u8: np.ndarray, sd: Dict, qp: Dict, residual: bool = True, upto: int | None = None,
+                 clips: Dict | None = None):
+    """uint8 NHWC frames, or float32 NCHW frames (the ``images['torch']`` layout; ``input_quant_f32``) -> (ori logits
+    f32, pos f32), or the integer activation after block ``upto`` (NCHW int64; 0 = stem output) / ``upto='last'`` (last
+    conv output) / ``upto='pool'``. ``clips``: a dict that receives, per requantising conv ('stem', 'blocks.N.expand' /
+    '.dw' / '.project', 'last'), (values below, values above) its output quantizer's range before the clip."""
     bits = _Bits(qp.get('bits'))
+
+    def rec(name):
+        return None if clips is None else clips.setdefault(name, [])
+
     slo, shi = -(1 << (bits.shared_act - 1)), (1 << (bits.shared_act - 1)) - 1
-    x = input_lut(qp['image'], bits.image)[frames_u8.astype(np.int64)].transpose(0, 3, 1, 2)       # NCHW int
+    if _np(frames_u8).dtype == np.uint8:
+        x = input_lut(qp['image'], bits.image)[_np(frames_u8).astype(np.int64)].transpose(0, 3, 1, 2)   # NCHW int
+    else:
+        assert _np(frames_u8).dtype == np.float32 and _np(frames_u8).shape[1] == 3, 'float frames are float32 NCHW'
+        x = input_quant_f32(frames_u8, qp['image'], bits.image)
     q, (M, B, S) = conv_requant_params(sd, f'{FP}.0', qp['image'], qp['stem'], bits.first_conv[0])
-    x = requant(_conv_int(x, q, 2, 1), M, B, S, 0, (1 << bits.first_conv[1]) - 1)
+    x = requant(_conv_int(x, q, 2, 1), M, B, S, 0, (1 << bits.first_conv[1]) - 1, clipped=rec('stem'))
     if upto == 0:
         return x
     s_x = qp['stem']
@@ -200,15 +224,15 @@ def int8_forward(frames_u8: np.ndarray, sd: Dict, qp: Dict, residual: bool = Tru
         y, j = x, 0
         if t != 1:
             q, (M, B, S) = conv_requant_params(sd, f'{FP}.{idx}.conv.0', s_in, bq['expand'], ew)
-            y = requant(_conv_int(y, q, 1, 1), M, B, S, 0, (1 << ea) - 1)
+            y = requant(_conv_int(y, q, 1, 1), M, B, S, 0, (1 << ea) - 1, clipped=rec(f'blocks.{idx}.expand'))
             s_y, j = bq['expand'], 1
         else:
             s_y = s_in
         q, (M, B, S) = conv_requant_params(sd, f'{FP}.{idx}.conv.{j}', s_y, bq['dw'], dwb)
-        y = requant(_conv_int(y, q, stride, q.shape[0]), M, B, S, 0, (1 << da) - 1)
+        y = requant(_conv_int(y, q, stride, q.shape[0]), M, B, S, 0, (1 << da) - 1, clipped=rec(f'blocks.{idx}.dw'))
         if res:
             q, (M, B, S) = conv_requant_params(sd, f'{FP}.{idx}.conv.{j + 1}', bq['dw'], s_q, pw)
-            p = requant(_conv_int(y, q, 1, 1), M, B, S, slo, shi)
+            p = requant(_conv_int(y, q, 1, 1), M, B, S, slo, shi, clipped=rec(f'blocks.{idx}.project'))
             R, RB, RS = fixed(s_q / s_next, 0.0)
             x = np.clip(((p + x) * R[0] + RB[0]) >> RS[0], slo, shi)
         else:
@@ -217,7 +241,7 @@ def int8_forward(frames_u8: np.ndarray, sd: Dict, qp: Dict, residual: bool = Tru
         if upto == idx:
             return x
     q, (M, B, S) = conv_requant_params(sd, f'{FP}.18', qp['final'], qp['last'], bits.last_conv[0])
-    x = requant(_conv_int(x, q, 1, 1), M, B, S, 0, (1 << bits.last_conv[1]) - 1)
+    x = requant(_conv_int(x, q, 1, 1), M, B, S, 0, (1 << bits.last_conv[1]) - 1, clipped=rec('last'))
     if upto == 'last':
         return x
     hw = x.shape[2] * x.shape[3]

@@ -148,3 +148,22 @@ def test_mse_calibration_option(model):
     o, _ = Q.int8_forward(fr, sd, qp)
     ro, _ = M.forward(M.u8_nhwc_to_nchw_f32(fr), sd)
     assert np.abs(o - ro.numpy()).max() < 0.08 * np.abs(ro.numpy()).max()
+
+
+def test_float_frame_entry(model):
+    """int8_forward on float32 NCHW frames: u8 / 255 gives the u8 entry's codes and outputs, and frames past [0, 1]
+    meet the input clip on both sides (with the calibrated image scale the clip is the signed quantizer's range)."""
+    sd, qp = model
+    fr = synth_frames(2, 64, 64, 5)
+    x = M.u8_nhwc_to_nchw_f32(fr).contiguous().numpy()
+    np.testing.assert_array_equal(Q.input_quant_f32(x, qp['image']),
+                                  Q.input_lut(qp['image'])[fr.astype(np.int64)].transpose(0, 3, 1, 2))
+    np.testing.assert_array_equal(Q.int8_forward(x, sd, qp, upto=2), Q.int8_forward(fr, sd, qp, upto=2))
+    for a, b in zip(Q.int8_forward(x, sd, qp), Q.int8_forward(fr, sd, qp)):
+        np.testing.assert_array_equal(a, b)
+    rng = np.random.default_rng(3)
+    wide = rng.uniform(-2.0, 2.0, (1, 3, 8, 8)).astype(np.float32)
+    q = Q.input_quant_f32(wide, qp['image'])
+    assert q.min() == -128 and q.max() == 127
+    inside = np.abs(wide / np.float32(qp['image'])) < 127
+    np.testing.assert_array_equal(q[inside], np.rint(wide / np.float32(qp['image']))[inside].astype(np.int64))
