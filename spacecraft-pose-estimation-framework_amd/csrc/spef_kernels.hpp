@@ -8,7 +8,7 @@
 
 namespace spef {
 
-// Sets the calling thread's spef_last_error() message and returns `code` (spef_api.cpp).
+// Sets the calling thread's spef_last_error() message and returns `code` (api_core.cpp).
 int report_error(int code, const std::string& msg);
 
 enum Dtype : int {

@@ -117,7 +117,7 @@ def test_headline_line_compact_on_a_full_gpu_record():
 
 def test_roofline_traffic_lookup_by_launched_kernel():
     """bench.py's PMC-traffic lookup for the roofline kernel: the profiling key names the kernel the library launched
-    (x2_irb / x2_irw / x2_irp, spef_api.cpp); each key must resolve to exactly one profiled instantiation of the
+    (x2_irb / x2_irw / x2_irp, api_schedule.cpp); each key must resolve to exactly one profiled instantiation of the
     committed round-6 fp16mx traffic file, and the dominant kernel's bytes must be the file's entry for it."""
     import json
     bench = _bench_module()
