@@ -106,6 +106,44 @@ int spef_set_decode_tables(spef_ctx* ctx, const double* ori_bins, int n_ori_bins
 int spef_decode(spef_ctx* ctx, int ori_mode, int pos_mode, const float* ori_raw, int n_ori, const float* pos_raw,
                 int n_pos, int B, float* ori_soft, float* quat, float* pos_soft, float* pos, int* status, void* stream);
 
+/* Pose covariance of the soft-classification decode (opt-in; nothing calls it unless asked): what the PDFs that
+ * spef_decode averaged say about the uncertainty of the pose it returned, as the measurement covariance
+ * spef_track_step takes (spef_amd/spe/decode_cov.py is the NumPy twin and the specification; DESIGN.md section 3,
+ * Covariance path). Works on any PDF + pose pair: spef_decode's ori_soft / pos_soft with its quat / pos, or
+ * spef_video_step's ori_filt / pos_filt with its quat / pos. All arithmetic is fp64, every sum in a fixed order: a
+ * row's result does not depend on the batch it is in.
+ *
+ * cov [B x 36]: row-major 6 x 6, order (theta_x, theta_y, theta_z, t_x, t_y, t_z), theta a left perturbation in the
+ *   camera frame (R = exp([theta]x) R^: the convention of spef_refine_keypoints and spef_track_step); the cross blocks
+ *   are zero.
+ *   theta block = sum_i p_i theta_i theta_i^T / sum_i p_i + floor_var[0] I, with theta_i the rotation vector of
+ *     q_i (x) conj(q^) on the hemisphere of scalar part >= 0 (the Log of the tracker's innovation), q_i the bins, q^ =
+ *     quat renormalised in fp64; every bin enters with its own p, redundant ones included, as in the Markley average.
+ *   t block = sum_i p_i (g_i - t^)(g_i - t^)^T / sum_i p_i + floor_var[1] I over the position grid g, t^ = pos (the
+ *     centred form).
+ *   A head in regression mode has no PDF: its block is fixed_var[k] I (the caller passes the tracker's r), and its
+ *     PDF, width and pose arguments are not read.
+ * ori_hinv (or NULL) [B x 16]: inv(a) of a = sum_i p_i q_i q_i^T, not normalised -- the second value of the
+ *   reference's OrientationSoftClassification.decode (classification_utils.py:142), rounded to float32. Orientation
+ *   classification only (SPEF_ERR_ARG otherwise).
+ * cov_status [B]: a word of its own, never ORed into the decode status (the scorer flags any row with a nonzero
+ *   decode status):
+ *     1  the orientation PDF or quat is not finite, quat is zero, or sum p <= 0: the theta block is NaN;
+ *     2  a is not positive definite to fp64 -- a Cholesky pivot that is not finite or not above 2^-48 of its diagonal
+ *        entry, which is what the rounding of the sums leaves of an exact zero (a one-hot PDF: the case where the
+ *        reference's np.linalg.inv raises LinAlgError): ori_hinv is NaN; the theta block stands;
+ *     4  the position PDF or pos is not finite, or sum p <= 0: the t block is NaN.
+ *   A row with a NaN block is a non-finite covariance to spef_track_step, which then uses its fixed r.
+ * Widths as in spef_decode: n_ori / n_pos must equal the tables' bin counts in classification mode (SPEF_ERR_ARG);
+ * SPEF_ERR_STATE when a table that is needed is not set. SPEF_ERR_ARG, with nothing enqueued, also for a NULL PDF or
+ * pose pointer of a head in classification mode, a NULL cov / cov_status / params, a negative or non-finite variance
+ * and B < 1. One launch, one workgroup per (row, head); no atomics, no allocation and no host synchronisation: it can
+ * follow spef_decode on a stream and be stream-captured. */
+typedef struct { double fixed_var[2], floor_var[2]; } spef_cov_params;
+int spef_decode_cov(spef_ctx* ctx, int ori_mode, int pos_mode, const float* ori_pdf, int n_ori, const float* pos_pdf,
+                    int n_pos, const float* quat, const float* pos, int B, const spef_cov_params* params, float* cov,
+                    float* ori_hinv, int* cov_status, void* stream);
+
 /* Adaptive video filter on the device: the reference's TemporalPDF.update_pdf (src/temporal/pdf_compare.py:94-134)
  * and the quaternion pole continuity of Inference.predict (src/temporal/inference.py:136-144, :173-180) for batches
  * of video frames. Frames are TIME-MAJOR: a batch of T * S rows holds T consecutive time steps of S independent

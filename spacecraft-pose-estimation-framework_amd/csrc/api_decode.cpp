@@ -1,5 +1,5 @@
-// Decode side of the C ABI (include/spef.h): decode tables and the classification / regression decode, the keypoint
-// model set-up for EPnP and its refinement, and the Pillow-exact resize.
+// Decode side of the C ABI (include/spef.h): decode tables, the classification / regression decode and the pose
+// covariance of its PDFs, the keypoint model set-up for EPnP and its refinement, and the Pillow-exact resize.
 #include <math.h>
 #include <string.h>
 
@@ -104,6 +104,47 @@ int spef_decode(spef_ctx* c, int ori_mode, int pos_mode, const float* ori_raw, i
   }
   if (pos_mode == SPEF_CLASSIFICATION)
     HIP_TRY(launch_decode_pos(pos_raw, B, c->n_pos_bins, c->d_pos_grid, pos_soft, pos, status, s));
+  return SPEF_OK;
+}
+
+int spef_decode_cov(spef_ctx* c, int ori_mode, int pos_mode, const float* ori_pdf, int n_ori, const float* pos_pdf,
+                    int n_pos, const float* quat, const float* pos, int B, const spef_cov_params* prm, float* cov,
+                    float* ori_hinv, int* cov_status, void* stream) {
+  if (!c) return fail(SPEF_ERR_ARG, "null context");
+  if (B < 1 || !prm || !cov || !cov_status) return fail(SPEF_ERR_ARG, "null argument");
+  if (ori_mode != SPEF_CLASSIFICATION && ori_mode != SPEF_REGRESSION)
+    return fail(SPEF_ERR_ARG, "ori_mode must be regression or classification");
+  if (pos_mode != SPEF_CLASSIFICATION && pos_mode != SPEF_REGRESSION)
+    return fail(SPEF_ERR_ARG, "pos_mode must be regression or classification");
+  for (int k = 0; k < 2; ++k)
+    if (!(prm->fixed_var[k] >= 0.0) || !std::isfinite(prm->fixed_var[k]) || !(prm->floor_var[k] >= 0.0) ||
+        !std::isfinite(prm->floor_var[k]))
+      return fail(SPEF_ERR_ARG, "fixed_var and floor_var must be finite and >= 0");
+  const bool oc = ori_mode == SPEF_CLASSIFICATION, pc = pos_mode == SPEF_CLASSIFICATION;
+  if (oc && (!ori_pdf || !quat)) return fail(SPEF_ERR_ARG, "orientation classification needs ori_pdf and quat");
+  if (pc && (!pos_pdf || !pos)) return fail(SPEF_ERR_ARG, "position classification needs pos_pdf and pos");
+  if (ori_hinv && !oc) return fail(SPEF_ERR_ARG, "ori_hinv needs the orientation head in classification mode");
+  if (oc && !c->d_ori_bins) return fail(SPEF_ERR_STATE, "orientation bins not set (spef_set_decode_tables)");
+  if (pc && !c->d_pos_grid) return fail(SPEF_ERR_STATE, "position grid not set (spef_set_decode_tables)");
+  if (oc && n_ori != c->n_ori_bins)
+    return fail(SPEF_ERR_ARG, "the orientation PDF is " + std::to_string(n_ori) + " wide, the histogram has " +
+                                  std::to_string(c->n_ori_bins) + " bins");
+  if (pc && n_pos != c->n_pos_bins)
+    return fail(SPEF_ERR_ARG, "the position PDF is " + std::to_string(n_pos) + " wide, the grid has " +
+                                  std::to_string(c->n_pos_bins) + " bins");
+  Dev d(c->device);
+  hipStream_t s = (hipStream_t)stream;
+  CovParams p;
+  for (int k = 0; k < 2; ++k) {
+    p.fixed_var[k] = prm->fixed_var[k];
+    p.floor_var[k] = prm->floor_var[k];
+  }
+  const double no = oc ? c->n_ori_bins : 0, np = pc ? c->n_pos_bins : 0;
+  HIP_TRY(prof_launch(c, s, "decode_cov_kernel", (double)B * (4.0 * no + 8.0 * np + 224.0) + 32.0 * no + 24.0 * np,
+                      (double)B * (no * 120.0 + np * 24.0), [&] {
+    return launch_decode_cov(oc, pc, ori_pdf, n_ori, c->d_ori_bins, pos_pdf, n_pos, c->d_pos_grid, quat, pos, B, p, cov,
+                             ori_hinv, cov_status, s);
+  }));
   return SPEF_OK;
 }
 

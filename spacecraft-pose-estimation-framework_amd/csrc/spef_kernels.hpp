@@ -168,6 +168,19 @@ hipError_t launch_decode_pos(const float* logits, int B, int n_bins, const doubl
 hipError_t launch_decode_pdf(const float* ori_pdf, const float* pos_pdf, int B, int n_ori, const double* q_bins,
                              int n_pos, const double* grid, float* quat, float* pos, int* status, hipStream_t s);
 
+// ---- pose covariance of the soft-classification decode (k_cov.hip; the arithmetic is stated in
+// spef_amd/spe/decode_cov.py) ----
+struct CovParams {
+  double fixed_var[2], floor_var[2];   // (theta, t): a regression head's variance; added to a classification head's diagonal
+};
+// cov [B][36] (theta first, then t), ori_hinv [B][16] (nullable; orientation classification only) and cov_status [B]
+// (1 theta block NaN, 2 a not positive definite, 4 t block NaN) from the PDFs [B][n] and the pose they were decoded to.
+// One launch, one workgroup per (row, head); a head that is not in classification mode (ori_cls / pos_cls = 0) reads
+// neither its PDF nor its table nor its pose.
+hipError_t launch_decode_cov(int ori_cls, int pos_cls, const float* ori_pdf, int n_ori, const double* q_bins,
+                             const float* pos_pdf, int n_pos, const double* grid, const float* quat, const float* pos,
+                             int B, const CovParams& prm, float* cov, float* ori_hinv, int* cov_status, hipStream_t s);
+
 // ---- adaptive video filter (k_video.hip; TemporalPDF.update_pdf, src/temporal/pdf_compare.py:94-134) ----
 // Frames are time-major: row t * S + s is time step t of stream s. One head (ori or pos) of the filter:
 struct VideoHead {

@@ -34,7 +34,8 @@ CXXFLAGS = ['-O3', '-fPIC', '-std=c++17', f'--offload-arch={ARCH}', '-Wall', '-W
 
 # Convolution kernels never see NaN (finite frames, finite folded weights): dropping NaN semantics lets the
 # compiler emit a single v_max_f32 per ReLU instead of canonicalize + max (~18 % fewer VALU ops in the fused
-# block loop). Decode / EPnP keep IEEE NaN semantics (they detect NaNs, classification_utils.py:134).
+# block loop). Decode / EPnP keep IEEE NaN semantics (they detect NaNs, classification_utils.py:134), and so do the
+# tracker and the decode covariance (k_track.hip, k_cov.hip: a NaN covariance is how a row says it has none).
 NO_NAN_SOURCES = {'k_irb.hip', 'k_irw.hip', 'k_irp.hip', 'k_front.hip', 'k_conv.hip', 'k_gemm.hip', 'k_pool.hip',
                   'k_x2.hip', 'k_mx.hip'}
 # The SLP vectorizer packs the depthwise FMAs into v_pk_fma_f32 with explicit fp16->fp32 converts (in the fused

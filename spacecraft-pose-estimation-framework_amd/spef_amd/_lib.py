@@ -40,6 +40,7 @@ SIGNATURES = {
     'spef_probe': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _ip, _ip, _ip, _vp]),
     'spef_set_decode_tables': (_i, [_vp, _vp, _i, _vp, _i]),
     'spef_decode': (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'spef_decode_cov': (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     'spef_video_create': (_i, [_vp, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(_vp)]),
     'spef_video_reset': (_i, [_vp, _i, _vp]),
     'spef_video_set_state': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -88,6 +89,13 @@ class TrackParams(C.Structure):   # spef_track_params
 
 
 TRACK_STATE_DOUBLES = 160
+
+
+class CovParams(C.Structure):     # spef_cov_params
+    _fields_ = [('fixed_var', C.c_double * 2), ('floor_var', C.c_double * 2)]
+
+
+COV_ORI, COV_HINV, COV_POS = 1, 2, 4   # spef_decode_cov's cov_status bits
 
 
 class SpefError(RuntimeError):

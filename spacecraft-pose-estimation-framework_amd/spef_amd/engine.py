@@ -231,7 +231,7 @@ class PoseTracker:
              want_rates: bool = False) -> dict:
         """``dec``: a decode dict of ``T * n_streams`` time-major rows: 'ori', 'pos', and when present 'status' (the
         decode status: rows with any of bits 1 | 2 | 4 | 8 are coasted over) and 'cov' ([B x 6 x 6], the pose
-        covariance of ``decode_keypoints(want_cov=True)``). -> {'ori', 'pos', 'mahalanobis', 'track_status'} and, when
+        covariance of ``decode_keypoints(want_cov=True)`` or of ``decode_cov``). -> {'ori', 'pos', 'mahalanobis', 'track_status'} and, when
         asked for, 'cov' [B x 6 x 6] (the pose block of P) and 'rates' [B x 6] (w, v) -- device tensors; the inputs are
         left as they are. ``engine`` is accepted for symmetry with ``VideoFilter.step``; the tracker needs no
         tables."""
@@ -484,7 +484,12 @@ class Engine:
         return out[:B * h.value * w.value * c.value].view(B, h.value, w.value, c.value)
 
     def decode(self, ori_mode: int, pos_mode: int, ori_raw: torch.Tensor, pos_raw: torch.Tensor,
-               want_soft: bool = True):
+               want_soft: bool = True, want_cov: bool = False, **cov_params):
+        """``want_cov`` (off by default): ``decode_cov`` follows the decode on the same stream and adds 'cov',
+        'cov_status' (and 'ori_hinv' with ``want_hinv=True``) to the dict; it needs the soft outputs, so they are
+        returned as well. ``cov_params``: fixed_var, floor_var, want_hinv."""
+        assert want_cov or not cov_params, 'fixed_var / floor_var / want_hinv go with want_cov'
+        want_soft = want_soft or want_cov
         B = ori_raw.shape[0]
         dev = self.device
         quat = torch.empty((B, 4), dtype=torch.float32, device=dev)
@@ -498,7 +503,45 @@ class Engine:
         L.check(self.lib.spef_decode(self.ctx, ori_mode, pos_mode, _ptr(ori_raw), ori_raw.shape[1], _ptr(pos_raw),
                                      pos_raw.shape[1], B, _ptr(ori_soft), _ptr(quat), _ptr(pos_soft), _ptr(pos),
                                      _ptr(status), _stream(dev)))
-        return {'ori': quat, 'pos': pos, 'ori_soft': ori_soft, 'pos_soft': pos_soft, 'status': status}
+        dec = {'ori': quat, 'pos': pos, 'ori_soft': ori_soft, 'pos_soft': pos_soft, 'status': status}
+        if want_cov:
+            self.decode_cov(dec, ori_mode, pos_mode, **cov_params)
+        return dec
+
+    def decode_cov(self, dec: dict, ori_mode: int, pos_mode: int, fixed_var=(100.0, 100.0), floor_var=(0.0, 0.0),
+                   want_hinv: bool = False) -> dict:
+        """The pose covariance of a soft-classification decode (csrc/k_cov.hip; ``spe.decode_cov`` is its NumPy twin
+        and states every quantity): adds 'cov' [B x 6 x 6] -- the measurement covariance ``PoseTracker.step`` reads,
+        order (theta, t) -- 'cov_status' [B] (1 theta block NaN, 2 the Markley matrix is not positive definite, 4 t
+        block NaN; a word of its own, the decode 'status' is left alone) and, with ``want_hinv``, 'ori_hinv'
+        [B x 4 x 4] (the inverse Markley matrix the reference's decode returns and drops) to ``dec`` and returns it.
+        ``dec`` is any PDF + pose pair: what ``decode`` returned, or ``VideoFilter.step``'s filtered PDFs with their
+        decode. A head in regression mode gets ``fixed_var[k]`` I (pass the tracker's ``r``); ``floor_var`` is added to
+        the diagonal of a classification head's block. One launch on the current stream; no host sync."""
+        quat, pos = dec['ori'], dec['pos']
+        B, dev = quat.shape[0], self.device
+        oc, pc = ori_mode == L.CLASSIFICATION, pos_mode == L.CLASSIFICATION
+        op, pp = (dec.get('ori_soft') if oc else None), (dec.get('pos_soft') if pc else None)
+        assert not oc or op is not None, 'decode_cov needs the orientation PDF (want_soft)'
+        assert not pc or pp is not None, 'decode_cov needs the position PDF (want_soft)'
+        assert not want_hinv or oc, 'ori_hinv needs the orientation head in classification mode'
+        for t in (quat, pos, op, pp):
+            assert t is None or (t.device == dev and t.is_contiguous() and t.dtype == torch.float32 and
+                                 t.shape[0] == B)
+        assert quat.shape == (B, 4) and pos.shape == (B, 3)
+        fx, fl = (np.asarray(v, np.float64).reshape(-1) for v in (fixed_var, floor_var))
+        assert fx.size == 2 and fl.size == 2, 'fixed_var and floor_var are (theta, t) pairs'
+        prm = L.CovParams((C.c_double * 2)(*fx), (C.c_double * 2)(*fl))
+        cov = torch.empty((B, 6, 6), dtype=torch.float32, device=dev)
+        hinv = torch.empty((B, 4, 4), dtype=torch.float32, device=dev) if want_hinv else None
+        cst = torch.empty((B,), dtype=torch.int32, device=dev)
+        L.check(self.lib.spef_decode_cov(self.ctx, ori_mode, pos_mode, _ptr(op), op.shape[1] if oc else 0, _ptr(pp),
+                                         pp.shape[1] if pc else 0, _ptr(quat), _ptr(pos), B, C.byref(prm), _ptr(cov),
+                                         _ptr(hinv), _ptr(cst), _stream(dev)))
+        dec['cov'], dec['cov_status'] = cov, cst
+        if want_hinv:
+            dec['ori_hinv'] = hinv
+        return dec
 
     def video_filter(self, n_streams: int, metric: str = 'l2', n_ori: float = 0.8, alpha_ori: float = 16.49,
                      n_pos: float = 0.5, alpha_pos: float = 48.64) -> 'VideoFilter':

@@ -18,7 +18,8 @@ decode and one video-filter step on the device (csrc/k_video.hip), sharing its s
 ``video_type='Tracker'`` (both calls; not in the reference, which ships a Kalman filter it never wires in) tracks the
 pose of any head, keypoint mode included, with the device tracker (csrc/k_track.hip, ``Engine.tracker``):
 ``pose_video`` = {'ori', 'pos', 'mahalanobis', 'track_status', 'keypoints', 'bbox'}. Its parameters are
-``Inference.tracker_params``; its state lives on the device and ``reset()`` clears it.
+``Inference.tracker_params``; its state lives on the device and ``reset()`` clears it. ``Inference.tracker_pdf_cov``
+(off by default) makes the measurement covariance that of the soft-classification PDFs (``Engine.decode_cov``).
 """
 from __future__ import annotations
 
@@ -61,6 +62,7 @@ class Inference:
         self.pdf_adapt_ori = TemporalPDF(n=0.8, alpha=16.49, distance_metric='l2')    # inference.py:38-39
         self.pdf_adapt_pos = TemporalPDF(n=0.5, alpha=48.64, distance_metric='l2')
         self.tracker_params = {}     # video_type 'Tracker': the parameters of Engine.tracker (q, p0, r, gate_chi2, ...)
+        self.tracker_pdf_cov = False  # video_type 'Tracker': SPEMi355x.predict_tracked(pdf_cov=True), the PDFs' covariance
         self.img_size = None
         self.device = device
         self.dtype = dtype
@@ -151,7 +153,8 @@ class Inference:
         if not hasattr(eng, 'predict_tracked'):
             raise ValueError("video filtering 'Tracker' needs the 'gpu_mi355x' engine")
         T = int(images.shape[0])
-        still, tracked, latency_ms = eng.predict_tracked(images, 1, **self.tracker_params)
+        pdf_cov = {'pdf_cov': True} if self.tracker_pdf_cov else {}
+        still, tracked, latency_ms = eng.predict_tracked(images, 1, **pdf_cov, **self.tracker_params)
         still = dict(still)
         still['ori'] = self._still_pole(still['ori'])
         out = []

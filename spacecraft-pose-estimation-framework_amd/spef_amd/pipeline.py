@@ -62,7 +62,8 @@ class StreamPipeline:
             e.reserve(B, H, W)
 
     def submit(self, frames: torch.Tensor, ori_mode: int = L.CLASSIFICATION, pos_mode: int = L.REGRESSION,
-               want_soft: bool = True, video=None, score=None, track=None) -> dict:
+               want_soft: bool = True, video=None, score=None, track=None, want_cov: bool = False,
+               floor_var=(0.0, 0.0)) -> dict:
         """Enqueue forward + decode of one batch on the next stream; returns the decode dict (device tensors,
         valid once that stream reaches them -- ``synchronize()`` or the dict's 'event').
 
@@ -82,7 +83,13 @@ class StreamPipeline:
         step is enqueued on the slot's stream after the decode, outside the recorded graph, and ordered after the
         previous submit's step through ``track.last_event`` exactly as ``video=`` is. The result is the dict's
         'track' entry (``PoseTracker.step``); with ``score`` as well, track 1 logs the tracked poses (flagged only
-        where a row passed through without a track)."""
+        where a row passed through without a track).
+
+        ``want_cov`` (off by default): ``Engine.decode_cov`` is enqueued on the slot's stream after the decode, outside
+        the recorded graph like the tracker step, and adds 'cov' / 'cov_status' to the dict -- so ``track=`` picks the
+        PDFs' own covariance up as the measurement covariance. A regression head gets the tracker's ``r`` (without a
+        tracker: ``spe.track.DEFAULTS['r']``); ``floor_var`` is added to a classification head's diagonal. Needs
+        ``want_soft``."""
         i = self._next
         self._next = (i + 1) % self.depth
         eng, s = self.engines[i], self.streams[i]
@@ -108,6 +115,15 @@ class StreamPipeline:
                 ev = torch.cuda.Event()
                 ev.record(s)
             dec['raw0'], dec['raw1'] = raw0, raw1
+            dec['event'] = ev
+        if want_cov:
+            assert want_soft, 'the covariance is computed from the soft PDFs'
+            from .spe.track import DEFAULTS
+            with torch.cuda.stream(s):
+                eng.decode_cov(dec, ori_mode, pos_mode, fixed_var=track.params['r'] if track is not None else
+                               DEFAULTS['r'], floor_var=floor_var)
+                ev = torch.cuda.Event()
+                ev.record(s)
             dec['event'] = ev
         if video is not None:
             with torch.cuda.stream(s):

@@ -103,10 +103,13 @@ class SPEMi355x:
         self.delete_model()
 
     # ------------------------------------------------------------------ inference
-    def _run(self, x: torch.Tensor):
+    def _run(self, x: torch.Tensor, want_cov: bool = False):
         raw0, raw1 = self.engine.forward(x)
         if self.keypoint_mode:   # sigmoid + batched EPnP on the GPU (spe_utils.py:66-68, keypoints_utils.py:152)
-            return raw0, None, self.engine.decode_keypoints(raw0, apply_sigmoid=True)
+            return raw0, None, self.engine.decode_keypoints(raw0, apply_sigmoid=True, want_cov=want_cov)
+        if want_cov:
+            return raw0, raw1, self.engine.decode(self.ori_mode, self.pos_mode, raw0, raw1, want_cov=True,
+                                                  want_hinv=self.ori_mode == L.CLASSIFICATION)
         return raw0, raw1, self.engine.decode(self.ori_mode, self.pos_mode, raw0, raw1)
 
     def predict_frames(self, frames: torch.Tensor, img_size, num_predict: int = 1) -> Tuple[Dict, float]:
@@ -124,8 +127,13 @@ class SPEMi355x:
         end.synchronize()
         return self._pose(dec), start.elapsed_time(end) / max(1, num_predict)
 
-    def predict(self, images: torch.Tensor, num_predict: int = 1) -> Tuple[Dict, float]:
-        """images: NCHW float32 in [0,1] (the reference ``images['torch']``) or NHWC uint8 frames."""
+    def predict(self, images: torch.Tensor, num_predict: int = 1, want_cov: bool = False) -> Tuple[Dict, float]:
+        """images: NCHW float32 in [0,1] (the reference ``images['torch']``) or NHWC uint8 frames.
+        ``want_cov`` (off by default): the pose dict also has 'cov' [B x 6 x 6], the pose covariance of the
+        soft-classification PDFs (``Engine.decode_cov``; order theta, t; a regression head's block is the default
+        fixed variance), its 'cov_status' and, behind an orientation classification head, 'ori_hinv' [B x 4 x 4], the
+        second value of the reference's orientation decode. In keypoint mode with ``keypoint_refine`` 'cov' is the
+        refinement's."""
         if self.engine is None:
             raise AssertionError('no model loaded')            # spe_torch.py:55 (assert hasattr(self, 'model'))
         x = images.to(self.device, non_blocking=True).contiguous()
@@ -133,11 +141,11 @@ class SPEMi355x:
         start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
         for _ in range(max(1, num_predict)):
-            raw0, raw1, dec = self._run(x)
+            raw0, raw1, dec = self._run(x, want_cov)
         end.record()
         end.synchronize()
         latency_ms = start.elapsed_time(end) / max(1, num_predict)
-        return self._pose(dec), latency_ms
+        return self._pose(dec, want_cov=want_cov), latency_ms
 
     # ------------------------------------------------------------------ video
     def video_filter(self, n_streams: int = 1, metric: str = 'l2', **params):
@@ -233,14 +241,18 @@ class SPEMi355x:
         self._track = None
 
     def predict_tracked(self, images: torch.Tensor, n_streams: int = 1, targets=None, scorer=None,
-                        **params) -> Tuple[Dict, Dict, float]:
+                        pdf_cov: bool = False, floor_var=(0.0, 0.0), **params) -> Tuple[Dict, Dict, float]:
         """Time-major video frames ``images`` [T * n_streams, ...] (row t * n_streams + s = step t of stream s) ->
         (still pose, tracked pose, latency ms) for every head mode: one batched forward, one decode and one tracker
         step (``Engine.tracker``: an error-state Kalman filter with gating and coasting), all on the GPU. The still
         pose is what ``predict`` returns, except that a row whose decode failed does not raise here: the tracker coasts
         over it and reports it in ``tracked['track_status']`` (bit 1; with bit 8 when the stream has no track yet and the
         row passes through). The tracked pose has 'ori', 'pos', 'mahalanobis' and 'track_status'. In keypoint mode with
-        ``keypoint_refine`` the refined pose's covariance is the measurement covariance; otherwise the fixed ``r`` is.
+        ``keypoint_refine`` the refined pose's covariance is the measurement covariance. Behind the URSONet heads
+        ``pdf_cov=True`` makes it the covariance of the soft-classification PDFs about their own decode
+        (``Engine.decode_cov`` with ``fixed_var`` = the tracker's ``r`` for a regression head and ``floor_var`` added to
+        a classification head's diagonal; a row whose PDF gives no covariance falls back to ``r``), which lets a
+        Mahalanobis gate fire; otherwise (the default) the fixed ``r`` is.
         The tracker's state persists between calls (``tracker(...).reset()`` starts new videos). ``params``: as
         ``Engine.tracker``. With ``targets`` and ``scorer`` (``engine.scorer(n_streams, 2, capacity)``) track 0 logs the
         still poses and track 1 the tracked ones; a tracked row counts as failed only where it passed through."""
@@ -257,6 +269,9 @@ class SPEMi355x:
         raw0, raw1 = self.engine.forward(x)
         if self.keypoint_mode:
             dec = self.engine.decode_keypoints(raw0, apply_sigmoid=True, want_cov=self.keypoint_refine is not None)
+        elif pdf_cov:
+            dec = self.engine.decode(self.ori_mode, self.pos_mode, raw0, raw1, want_cov=True, fixed_var=trk.params['r'],
+                                     floor_var=floor_var)
         else:
             dec = self.engine.decode(self.ori_mode, self.pos_mode, raw0, raw1)
         out = trk.step(dec, B // n_streams)
@@ -271,7 +286,7 @@ class SPEMi355x:
         tracked = {k: out[k].cpu().numpy() for k in ('ori', 'pos', 'mahalanobis', 'track_status')}
         return self._pose(dec, check=False), tracked, start.elapsed_time(end)
 
-    def _pose(self, dec, check: bool = True) -> Dict:
+    def _pose(self, dec, check: bool = True, want_cov: bool = False) -> Dict:
         status = dec['status'].cpu().numpy() if check else np.zeros(1, np.int32)
         if np.any(status & 1):
             raise ValueError('Error during orientation decoding')                       # classification_utils.py:135
@@ -290,6 +305,8 @@ class SPEMi355x:
                 pose['ori_epnp'] = dec['ori_epnp'].cpu().numpy()
                 pose['pos_epnp'] = dec['pos_epnp'].cpu().numpy()
                 pose['reproj_rms'] = dec['fit'][:, :2].cpu().numpy()
+            if want_cov and 'cov' in dec:
+                pose['cov'] = dec['cov'].cpu().numpy()
             return pose
 
         pose = {'ori': dec['ori'].cpu().numpy(), 'pos': dec['pos'].cpu().numpy()}
@@ -297,4 +314,7 @@ class SPEMi355x:
             pose['ori_soft'] = dec['ori_soft'].cpu().numpy()
         if self.pos_mode == L.CLASSIFICATION:
             pose['pos_soft'] = dec['pos_soft'].cpu().numpy()
+        for k in ('cov', 'cov_status', 'ori_hinv') if want_cov else ():
+            if k in dec:
+                pose[k] = dec[k].cpu().numpy()
         return pose
