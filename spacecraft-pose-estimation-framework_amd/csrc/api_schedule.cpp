@@ -94,7 +94,7 @@ struct Run {
                               // written (spef_amd.quant.calibrate's taps; spef_observe)
   int dt;
   bool f32;    // fp32 schedule: one kernel per conv (k_f32.hip), no fused kernels
-  bool x2;     // fp16x2 kernels: fused split-fp16 blocks (k_x2.hip)
+  bool x2;     // fp16x2 kernels: fused split-fp16 blocks (k_x2_*.hip)
   bool mx;     // fp16mx: the same weights; the block outputs with <= 24 channels (blocks 1-3: the 256^2 / 128^2 maps,
                // DESIGN.md section 5) are stored fp16, every other block output fp32
   double es;   // activation bytes per element (profiler byte counts)
@@ -198,12 +198,17 @@ int irb_step_x2(const Run& r, const OpDesc& op, const Block& g, Act& a) {
   const int B = r.B, h = a.h, w = a.w, OH = g.OH, OW = g.OW;
   void* x = a.p;
   const bool cur16 = a.f16;
-  if (!x2_irb_supported(g.cin, g.hid, g.cout, g.stride, g.expand, g.res))
-    return fail(SPEF_ERR_ARG, "fp16x2 schedule: unsupported inverted-residual geometry");
   void* y = free_buf(c, {x});
   const double hp = (op.hidden + 31) & ~31u;
   const bool o16 = r.out16(op);
   const int io = (cur16 ? 1 : 0) | (o16 ? 2 : 0);
+  // a third activation buffer (each holds the largest map) is the hidden-split form's partial-sum scratch
+  float* scratch = (float*)free_buf(c, {x, y});
+  // one plan: the support check, the profiling label and the launch all read it
+  const X2Block blk{g.cin, g.hid, g.cout, g.stride, g.expand, g.res};
+  const int cus = num_cus();
+  const X2Plan plan = x2_irb_plan(blk, B, OH, OW, scratch != nullptr, io, cus);
+  if (!plan.known) return fail(SPEF_ERR_ARG, "fp16x2 schedule: unsupported inverted-residual geometry");
   const double ib = cur16 ? 2 : 4, ob = o16 ? 2 : 4;
   // compulsory bytes: the block input once (a stride-1 residual IS that input: not counted twice), the output,
   // the weights once (the fp16 formula of irb_step_fused16 counts the same way)
@@ -217,17 +222,15 @@ int irb_step_x2(const Run& r, const OpDesc& op, const Block& g, Act& a) {
   const bool mxlean = (c->trim & 2) != 0;
   const char* kn = mxk ? (mxlean && !mx_irb_lean_fits(g.cin, g.cout, o16, h, w, OH, OW) ? "mx_irb_kernel_wide"
                                                                                        : "mx_irb_kernel")
-                       : x2_irb_kernel_name(g.cin, g.hid, g.cout, g.stride, g.expand, g.res, B, OH, OW, true, io,
-                                            num_cus());
+                       : plan.kernel_name();
   snprintf(key, sizeof(key), "%s<%u,%u,%u,s%u>", kn ? kn : "x2_irb_kernel", op.cin, op.hidden, op.cout, op.stride);
   const Wts wt = weights(c, op);
   HIP_TRY(prof_launch(c, s, key, bytes, irb_flops(op, g), [&] {
     if (mxk)
       return launch_mx_irb(g.cin, g.hid, g.cout, g.stride, g.res, cur16, o16, x, wt.w0, wt.b0, (const float*)wt.w1,
                            wt.b1, wt.w2, wt.b2, y, B, h, w, OH, OW, s, mxlean);
-    // a third activation buffer (each holds the largest map) is the hidden-split form's partial-sum scratch
-    return launch_x2_irb(g.cin, g.hid, g.cout, g.stride, g.expand, g.res, x, wt.w0, wt.b0, (const float*)wt.w1, wt.b1,
-                         wt.w2, wt.b2, y, B, h, w, OH, OW, s, (float*)free_buf(c, {x, y}), io);
+    return launch_x2_irb(blk, plan, {x, wt.w0, wt.b0, (const float*)wt.w1, wt.b1, wt.w2, wt.b2, y, B, h, w, OH, OW,
+                                     scratch, io, cus}, s);
   }));
   advance(a, y, OH, OW, op.cout, o16);
   return SPEF_OK;

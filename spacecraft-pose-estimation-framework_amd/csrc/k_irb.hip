@@ -962,20 +962,14 @@ static hipError_t irb_go(const void* x, const void* we, const float* be, const v
   constexpr bool PKU = irb_pku(irb_pk(std::is_same<DT, F16>::value, HID, EXPAND, S) && ABL == 0, NW, DBUF, STW, S, TH, TW);
   using G = IrbGeom<CIN, HID, COUT, S, TH, TW, EXPAND, RES, NW, WCO, DBUF, STW, (int)sizeof(DW), VP, PKU>;
   using T = typename DT::T;
-  const int tiles_x = (OW + TW - 1) / TW, tiles_y = (OH + TH - 1) / TH;
-  const int64_t nwg64 = (int64_t)tiles_x * tiles_y * B;
-  if (nwg64 > 0x7fffffff) return hipErrorInvalidValue;
-  const uint32_t nwg = (uint32_t)nwg64;
-  const size_t lds = (size_t)G::LDS_BYTES;
+  TileGrid g;
+  hipError_t e = tile_grid(g, OH, OW, TH, TW, B);
+  if (e != hipSuccess) return e;
   auto k = irb_kernel<DT, CIN, HID, COUT, S, TH, TW, EXPAND, RES, NW, WCO, DBUF, STW, ABL>;
-  static DevOnce attr_set;   // > 64 KiB dynamic LDS needs the attribute (once per instantiation)
-  if (!attr_set.done() && lds > 65536) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
-  k<<<nwg, NW * 64, lds, s>>>((const T*)x, (const T*)we, be, (const DW*)wd, bd, (const T*)wp, bp, (T*)y, H, W, OH, OW, tiles_x,
-                              tiles_y, nwg);
+  static DevOnce attr_set;
+  if ((e = lds_attr_once(attr_set, k, G::LDS_BYTES)) != hipSuccess) return e;
+  k<<<g.nwg, NW * 64, G::LDS_BYTES, s>>>((const T*)x, (const T*)we, be, (const DW*)wd, bd, (const T*)wp, bp, (T*)y, H, W,
+                                         OH, OW, g.tiles_x, g.tiles_y, g.nwg);
   return hipGetLastError();
 }
 

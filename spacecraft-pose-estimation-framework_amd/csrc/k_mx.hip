@@ -27,8 +27,8 @@
 // Two barriers per chunk (slab ready; exchange ready).
 #include <type_traits>
 
-#include "spef_common.hpp"
 #include "spef_kernels.hpp"
+#include "x2_common.hpp"   // lo_pair, mfma_x2
 
 namespace spef {
 
@@ -66,20 +66,6 @@ constexpr bool b128_group_same() {   // (the branchy form restated: a constexpr 
   return true;
 }
 static_assert(b128_group_same(), "b128_group_lean");
-
-__device__ __forceinline__ uint32_t lo_pair_mx(uint32_t hi2, float a, float b) {
-  uint32_t r;
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "=&v"(r) : "v"(hi2), "v"(a), "v"(b));
-  return r;
-}
-
-__device__ __forceinline__ f32x4 mfma3(f16x8 ah, f16x8 al, f16x8 bh, f16x8 bl, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc, 0, 0, 0);
-}
 
 }  // namespace
 
@@ -387,7 +373,7 @@ void mx_irb_kernel(const void* __restrict__ X, const _Float16* __restrict__ We, 
       for (int e = 0; e < 4; ++e) {
         const float x0 = fmaxf(a[t][2 * e], 0.f), x1 = fmaxf(a[t][2 * e + 1], 0.f);
         hh[e] = pack_h2((_Float16)x0, (_Float16)x1);
-        ll[e] = lo_pair_mx(hh[e], x0, x1);
+        ll[e] = lo_pair(hh[e], x0, x1);
       }
       const int px = (ry * G::PPL + t) * TW + cx;
       const int o = (LEAN ? lmul(ry * G::PPL * TW + cx, G::DXB) + t * (TW * G::DXB) : px * G::DXB) + skw + 16 * wave;
@@ -406,7 +392,7 @@ void mx_irb_kernel(const void* __restrict__ X, const _Float16* __restrict__ We, 
       const f16x8 bh = *reinterpret_cast<const f16x8*>(Dh + o);
       const f16x8 bl = *reinterpret_cast<const f16x8*>(Dl + o);
 #pragma unroll
-      for (int t = 0; t < G::NCT; ++t) acc[i][t] = mfma3(pah[t], pal[t], bh, bl, acc[i][t]);
+      for (int t = 0; t < G::NCT; ++t) acc[i][t] = mfma_x2(pah[t], pal[t], bh, bl, acc[i][t]);
     }
     if (c + 1 < G::NCH) load_p(c + 1);
     __syncthreads();   // exchange reads done before the next expand overlays them
@@ -470,28 +456,21 @@ template <int CIN, int HID, int COUT, int S, int TH, bool RES, bool IN16, bool O
 static hipError_t mx_go(const void* x, const void* we, const float* be, const float* wd, const float* bd,
                         const void* wp, const float* bp, void* y, int B, int H, int W, int OH, int OW, hipStream_t s) {
   using G = MxGeom<CIN, HID, COUT, S, TH>;
-  const int tiles_x = (OW + G::TW - 1) / G::TW, tiles_y = (OH + TH - 1) / TH;
-  const int64_t nwg64 = (int64_t)tiles_x * tiles_y * B;
-  if (nwg64 > 0x7fffffff) return hipErrorInvalidValue;
-  const uint32_t nwg = (uint32_t)nwg64;
+  TileGrid g;
+  hipError_t e = tile_grid(g, OH, OW, TH, G::TW, B);
+  if (e != hipSuccess) return e;
   auto k = mx_irb_kernel<CIN, HID, COUT, S, TH, RES, IN16, OUT16, LEAN>;
-  if (G::LDS_BYTES > 65536) {
-    static DevOnce attr_set;   // per device
-    if (!attr_set.done()) {
-      hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-      if (e != hipSuccess) return e;
-      attr_set.set();
-    }
-  }
-  k<<<nwg, 256, G::LDS_BYTES, s>>>(x, (const _Float16*)we, be, wd, bd, (const _Float16*)wp, bp, y, H,
-                                   W, OH, OW, tiles_x, tiles_y, nwg);
+  static DevOnce attr_set;
+  if ((e = lds_attr_once(attr_set, k, G::LDS_BYTES)) != hipSuccess) return e;
+  k<<<g.nwg, 256, G::LDS_BYTES, s>>>(x, (const _Float16*)we, be, wd, bd, (const _Float16*)wp, bp, y, H,
+                                     W, OH, OW, g.tiles_x, g.tiles_y, g.nwg);
   return hipGetLastError();
 }
 
 // (cin, hidden, cout, stride, residual, fp16 input, fp16 output, tile rows): blocks 2-4 of MobileNet-V2
 // (mobilenet_v2.py:240-249) in the fp16mx schedule -- fp16 block outputs for blocks 1-3 (the 256^2 / 128^2 maps),
 // fp32 from block 4 on; the output tile is TH x 16. Blocks 5-7 keep an fp32 hidden tensor (the fp16x2 slab kernel,
-// k_x2.hip): their fp16 hidden storage would add 31 % to the schedule's logit error variance
+// k_x2_irb.hip): their fp16 hidden storage would add 31 % to the schedule's logit error variance
 // (tools/precision_budget.py: rms 1.21e-4 -> 1.46e-4 on the parity tests' frames) for 32 us of a ~1.3 ms step.
 #define SPEF_MX_TABLE(X)                                \
   X(16, 96, 24, 2, false, true, true, 8)     /* 2 */     \
@@ -788,9 +767,9 @@ __global__ __launch_bounds__(NW * 64) void front_mx_kernel(
       for (int e = 0; e < 4; ++e) {
         const float x0 = fmaxf(av[2 * e], 0.f), x1 = fmaxf(av[2 * e + 1], 0.f);
         hh[e] = pack_h2((_Float16)x0, (_Float16)x1);
-        ll[e] = lo_pair_mx(hh[e], x0, x1);
+        ll[e] = lo_pair(hh[e], x0, x1);
       }
-      acc[h] = mfma3(pah, pal, __builtin_bit_cast(f16x8, make_uint4(hh[0], hh[1], hh[2], hh[3])),
+      acc[h] = mfma_x2(pah, pal, __builtin_bit_cast(f16x8, make_uint4(hh[0], hh[1], hh[2], hh[3])),
                      __builtin_bit_cast(f16x8, make_uint4(ll[0], ll[1], ll[2], ll[3])), acc[h]);
     }
     const int gy = oy0 + oy, gx = ox0 + ox;

@@ -371,20 +371,16 @@ hipError_t q_irb_go(const int8_t* x, const int8_t* we, const int8_t* wp, const i
                     hipStream_t s) {
   if (qb.eb < 2 || qb.eb > 8 || qb.db < 2 || qb.db > 8 || qb.sb < 2 || qb.sb > 8) return hipErrorInvalidValue;
   using G = QGeom<CIN, HID, COUT, S, TH, TW, RES, NW>;
-  const int tiles_x = (OW + TW - 1) / TW, tiles_y = (OH + TH - 1) / TH;
-  const int64_t nwg64 = (int64_t)tiles_x * tiles_y * B;
-  if (nwg64 > 0x7fffffff) return hipErrorInvalidValue;
-  const uint32_t nwg = (uint32_t)nwg64;
+  TileGrid g;
+  hipError_t e = tile_grid(g, OH, OW, TH, TW, B);
+  if (e != hipSuccess) return e;
   auto k = q_irb_kernel<CIN, HID, COUT, S, TH, TW, RES, NW, EXPAND, SH32>;
   constexpr int lds = G::LDS_BYTES - ((EXPAND || RES) ? 0 : G::PINP * G::XSB);   // see XREG in the kernel
   static DevOnce attr_set;
-  if (!attr_set.done() && lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
-  k<<<nwg, NW * 64, lds, s>>>(x, we, wp, pinit, tabs, rm, rb, rs, (1 << qb.eb) - 1, (1 << qb.db) - 1,
-                              -(1 << (qb.sb - 1)), (1 << (qb.sb - 1)) - 1, y, H, W, OH, OW, tiles_x, tiles_y, nwg);
+  if ((e = lds_attr_once(attr_set, k, lds)) != hipSuccess) return e;
+  k<<<g.nwg, NW * 64, lds, s>>>(x, we, wp, pinit, tabs, rm, rb, rs, (1 << qb.eb) - 1, (1 << qb.db) - 1,
+                                -(1 << (qb.sb - 1)), (1 << (qb.sb - 1)) - 1, y, H, W, OH, OW, g.tiles_x, g.tiles_y,
+                                g.nwg);
   return hipGetLastError();
 }
 

@@ -368,20 +368,15 @@ hipError_t q_irw_go(const int8_t* x, const int8_t* we, const int8_t* wp, const i
                     hipStream_t s) {
   if (qb.eb < 2 || qb.eb > 8 || qb.db < 2 || qb.db > 8 || qb.sb < 2 || qb.sb > 8) return hipErrorInvalidValue;
   using G = QwGeom<CIN, HID, COUT, S, TH, TW, NE, ND>;
-  const int tiles_x = (OW + TW - 1) / TW, tiles_y = (OH + TH - 1) / TH;
-  const int64_t nwg64 = (int64_t)tiles_x * tiles_y * B;
-  if (nwg64 > 0x7fffffff) return hipErrorInvalidValue;
-  const uint32_t nwg = (uint32_t)nwg64;
+  TileGrid g;
+  hipError_t e = tile_grid(g, OH, OW, TH, TW, B);
+  if (e != hipSuccess) return e;
   auto k = q_irw_kernel<CIN, HID, COUT, S, TH, TW, RES, NE, ND, SH32>;
   static DevOnce attr_set;
-  if (!attr_set.done() && G::LDS_BYTES > 65536) {
-    const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
-  k<<<nwg, G::NW * 64, G::LDS_BYTES, s>>>(x, we, wp, pinit, tabs, rm, rb, rs, (1 << qb.eb) - 1, (1 << qb.db) - 1,
-                                          -(1 << (qb.sb - 1)), (1 << (qb.sb - 1)) - 1, y, H, W, OH, OW, tiles_x,
-                                          tiles_y, nwg);
+  if ((e = lds_attr_once(attr_set, k, G::LDS_BYTES)) != hipSuccess) return e;
+  k<<<g.nwg, G::NW * 64, G::LDS_BYTES, s>>>(x, we, wp, pinit, tabs, rm, rb, rs, (1 << qb.eb) - 1, (1 << qb.db) - 1,
+                                            -(1 << (qb.sb - 1)), (1 << (qb.sb - 1)) - 1, y, H, W, OH, OW, g.tiles_x,
+                                            g.tiles_y, g.nwg);
   return hipGetLastError();
 }
 

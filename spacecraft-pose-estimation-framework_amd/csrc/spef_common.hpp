@@ -21,6 +21,32 @@ struct DevOnce {
   void set() { mask |= 1u << dev(); }
 };
 
+// More than 64 KiB of dynamic LDS needs the kernel's attribute raised first: once per device, through the caller's
+// flag (a static one per kernel instantiation).
+template <typename K>
+inline hipError_t lds_attr_once(DevOnce& once, K kernel, int lds_bytes) {
+  if (lds_bytes <= 65536 || once.done()) return hipSuccess;
+  const hipError_t e =
+      hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  if (e == hipSuccess) once.set();
+  return e;
+}
+
+// The grid of a tiled block kernel: one workgroup per TH x TW output tile, image and part (the kernels decode a
+// 32-bit workgroup index: 2^31 workgroups or more are refused).
+struct TileGrid {
+  int tiles_x = 0, tiles_y = 0;
+  uint32_t nwg = 0;
+};
+inline hipError_t tile_grid(TileGrid& g, int OH, int OW, int TH, int TW, int B, int parts = 1) {
+  g.tiles_x = (OW + TW - 1) / TW;
+  g.tiles_y = (OH + TH - 1) / TH;
+  const int64_t nwg64 = (int64_t)g.tiles_x * g.tiles_y * B * parts;
+  if (nwg64 > 0x7fffffff) return hipErrorInvalidValue;
+  g.nwg = (uint32_t)nwg64;
+  return hipSuccess;
+}
+
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

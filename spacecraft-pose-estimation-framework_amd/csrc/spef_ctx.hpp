@@ -171,7 +171,7 @@ static inline const T* ptr(const spef_ctx* c, uint64_t off) {
 // quantizer bit width of an int8 op (spef_blob.hpp qbits; 0 = 8)
 static inline int qbits(const OpDesc& op, int i) { return op.qbits[i] ? op.qbits[i] : 8; }
 
-// compute units of the current device (cached per device; launch_x2_irb sizes its tiles by the same query)
+// compute units of the current device (cached per device; the fp16x2 plan sizes its tiles by it)
 SPEF_INTERNAL int num_cus();
 SPEF_INTERNAL int check_ready(spef_ctx* c, int B, int H, int W);
 SPEF_INTERNAL void free_workspace(spef_ctx* c);

@@ -6,6 +6,8 @@
 
 #include <string>
 
+#include "x2_plan.hpp"
+
 namespace spef {
 
 // Sets the calling thread's spef_last_error() message and returns `code` (api_core.cpp).
@@ -13,7 +15,7 @@ int report_error(int code, const std::string& msg);
 
 enum Dtype : int {
   DT_F16 = 1, DT_BF16 = 2, DT_I8 = 3, DT_F32 = 4,
-  DT_X2 = 5,   // fp32 I/O, split-fp16 MFMA (k_x2.hip)
+  DT_X2 = 5,   // fp32 I/O, split-fp16 MFMA (k_x2_*.hip)
   DT_MX = 6    // fp16mx: the fp16x2 weights; stem map, block outputs of blocks 1-3, hidden of blocks 2-4 stored fp16
 };
 enum Epi : int { EPI_NONE = 0, EPI_RELU = 1, EPI_RES = 2, EPI_RELU_F32 = 3 /* ReLU, fp32 output */ };
@@ -85,19 +87,36 @@ hipError_t launch_front(int dtype, const void* x, const void* wsp, const float* 
 hipError_t launch_gemm_f32(int epi, const void* x, const void* wt, const float* bias, const void* r, void* y,
                            int64_t M, int K, int N, hipStream_t s);
 const char* gemm_f32_key(int N);
-// fp16x2 schedule (k_x2.hip, blob dtype 5): fused inverted residual on fp32 NHWC activations with hi + lo fp16
-// operands (3 MFMAs per product). we: [2][r32(hid)][r32(cin)] fp16 (hi plane, lo plane), be fp32 [r32(hid)],
-// wd fp32 [9][r32(hid)], bd fp32 [r32(hid)], wp [2][r16(cout)][r32(hid)] fp16, bp fp32 [r16(cout)]; zero padded.
+// fp16x2 schedule (k_x2_*.hip, blob dtype 5): fused inverted residual on fp32 NHWC activations with hi + lo fp16
+// operands (3 MFMAs per product). x2_irb_plan (x2_plan.hpp) picks the kernel and its tile; the two queries below
+// are that plan's `known` and kernel_name() ("x2_irb_kernel" / "x2_irw_kernel" / "x2_irp_kernel", nullptr when none).
 bool x2_irb_supported(int cin, int hid, int cout, int stride, bool expand, bool res);
-// the kernel launch_x2_irb runs for these arguments ("x2_irb_kernel" / "x2_irw_kernel" / "x2_irp_kernel"; profiling
-// labels), nullptr when none
 const char* x2_irb_kernel_name(int cin, int hid, int cout, int stride, bool expand, bool res, int B, int OH, int OW,
                                bool scratch, int io, int num_cu);
+// we: [2][r32(hid)][r32(cin)] fp16 (hi plane, lo plane), be fp32 [r32(hid)], wd fp32 [9][r32(hid)], bd fp32
+// [r32(hid)], wp [2][r16(cout)][r32(hid)] fp16, bp fp32 [r16(cout)]; zero padded.
 // scratch (nullable): B * OH * OW * cout * 2 floats for the hidden-split form of the late blocks on small maps.
 // io: bit 0 = fp16 input x, bit 1 = fp16 output y (the fp16mx schedule; slab-kernel geometries, blocks 1-7, only).
-hipError_t launch_x2_irb(int cin, int hid, int cout, int stride, bool expand, bool res, const void* x, const void* we,
-                         const float* be, const float* wd, const float* bd, const void* wp, const float* bp, void* y,
-                         int B, int H, int W, int OH, int OW, hipStream_t s, float* scratch = nullptr, int io = 0);
+// num_cu: the compute-unit count the plan was made with (the persistent-tile kernels size their grid by it).
+struct X2Args {
+  const void* x;
+  const void* we;
+  const float *be, *wd, *bd;
+  const void* wp;
+  const float* bp;
+  void* y;
+  int B, H, W, OH, OW;
+  float* scratch;
+  int io, num_cu;
+};
+// Runs the plan's row (hipErrorNotSupported when the plan found none); the plan must come from x2_irb_plan with
+// this block, a.B, a.OH, a.OW, a.scratch != nullptr, a.io and a.num_cu.
+hipError_t launch_x2_irb(const X2Block& b, const X2Plan& p, const X2Args& a, hipStream_t s);
+// The families' part of it: the rows of the plan's kind -> the template instantiation (k_x2_irb.hip kind 0,
+// k_x2_irw.hip kinds 1-3, k_x2_irp.hip kinds 5-6).
+hipError_t launch_x2_slab(const X2Block& b, const X2Plan& p, const X2Args& a, hipStream_t s);
+hipError_t launch_x2_split(const X2Block& b, const X2Plan& p, const X2Args& a, hipStream_t s);
+hipError_t launch_x2_stage3(const X2Block& b, const X2Plan& p, const X2Args& a, hipStream_t s);
 // fp16mx blocks 2-4 (k_mx.hip): fp16 input, hi + lo fp16 weights (blob dtype 5 / 6 layout), fp16 hidden slab, fp32
 // depthwise, hi + lo project operand; fp16 (out16: blocks 2-3) or fp32 (block 4) output.
 bool mx_irb_supported(int cin, int hid, int cout, int stride, bool expand, bool res, bool in16, bool out16);

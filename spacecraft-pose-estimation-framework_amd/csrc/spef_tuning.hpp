@@ -11,7 +11,7 @@
 //                         kernels with fp16 block I/O (0).
 //   SPEF_OPT_TRIM       : kernels that drop work the result does not need, bit-identical to the ones they replace (an
 //                         A/B switch, one bit per kernel). Bit 0: the fp16x2 / fp16mx last conv on the 128-pixel x
-//                         320-channel staged tile (k_x2.hip) instead of 64 x 256. Bit 1: the fp16mx blocks 2-4
+//                         320-channel staged tile (k_x2_pw.hip) instead of 64 x 256. Bit 1: the fp16mx blocks 2-4
 //                         (k_mx.hip mx_irb_kernel) with the lean tile set-up -- scalar image bases, 32-bit per-lane
 //                         offsets, incremental tile pixels, no bounds checks in interior workgroups -- instead of 64-bit
 //                         per-pixel addresses (a map too large for the offsets runs the earlier form whatever the bit,

@@ -37,7 +37,7 @@ CXXFLAGS = ['-O3', '-fPIC', '-std=c++17', f'--offload-arch={ARCH}', '-Wall', '-W
 # block loop). Decode / EPnP keep IEEE NaN semantics (they detect NaNs, classification_utils.py:134), and so do the
 # tracker and the decode covariance (k_track.hip, k_cov.hip: a NaN covariance is how a row says it has none).
 NO_NAN_SOURCES = {'k_irb.hip', 'k_irw.hip', 'k_irp.hip', 'k_front.hip', 'k_conv.hip', 'k_gemm.hip', 'k_pool.hip',
-                  'k_x2.hip', 'k_mx.hip'}
+                  'k_x2_irb.hip', 'k_x2_irw.hip', 'k_x2_irp.hip', 'k_x2_front.hip', 'k_x2_pw.hip', 'k_mx.hip'}
 # The SLP vectorizer packs the depthwise FMAs into v_pk_fma_f32 with explicit fp16->fp32 converts (in the fused
 # block kernels as soon as their outputs are converted pairwise); scalar v_fma_mix_f32 (fp16 operands read in place)
 # is fewer instructions, and every fp32 VALU op costs the same 4 cycles (profiles/r01_valu_rate.txt).

@@ -11,7 +11,7 @@ Pointwise weights are stored [Np][Kp] in the activation dtype (fp16 default, bf1
 (Kp = K up to a multiple of 32, Np = N up to a multiple of 16) so the MFMA kernels never mask weight loads.
 Depthwise weights are fp16 in fp16 blobs (fp32 in bf16 blobs); stem, bias and head weights stay fp32.
 
-``fp16x2`` (dtype 5, the fp32-accurate fused schedule of csrc/k_x2.hip): every 1x1 weight is stored as two fp16
+``fp16x2`` (dtype 5, the fp32-accurate fused schedule of csrc/k_x2_*.hip): every 1x1 weight is stored as two fp16
 planes [2][rows][Kp], hi = fp16(w) and lo = fp16(w - hi) of the float64 folded weight (22 significant bits), expand
 rows padded to 32; depthwise weights fp32 [9][H32] and the hidden-width biases padded to H32 = hidden rounded up to
 32 (zeros), so the kernel never masks a channel; the stem's /255-folded MFMA operand x0 as [2][3 ky][32][32] hi / lo
@@ -34,7 +34,7 @@ from .arch import Arch, BN_EPS, ConvSpec, LAST_CHANNELS, arch_from_state_dict, m
 MAGIC = b'SPEFMI35'
 VERSION = 2   # 2: fp16 stem MFMA operand in the front_vp_kernel row-triple k order (csrc/spef_blob.hpp)
 DTYPES = {'fp16': 1, 'bf16': 2, 'fp32': 4, 'fp16x2': 5, 'fp16mx': 6}   # fp32: the reference's own arithmetic
-# (k_f32.hip); fp16x2: fp32 activations with hi + lo fp16 MFMA operands (k_x2.hip); fp16mx: the same weights,
+# (k_f32.hip); fp16x2: fp32 activations with hi + lo fp16 MFMA operands (k_x2_*.hip); fp16mx: the same weights,
 # fp16 stem map, block outputs of blocks 1-3, hidden tensors of blocks 2-4
 X2_DTYPES = ('fp16x2', 'fp16mx')   # the split-fp16 weight layout
 DT_I8 = 3

@@ -168,7 +168,7 @@ class Restated:
     """One network's folded weights in float64 and its blocks under a schedule's rounding points.
 
     A 1x1 conv of the hi + lo schedules is the kernels' three-MFMA sum w_hi x_hi + w_lo x_hi + w_hi x_lo with
-    hi = fp16(v), lo = fp16(f32(v) - hi) for weight and activation alike (csrc/k_x2.hip split8 / mfma_x2), the
+    hi = fp16(v), lo = fp16(f32(v) - hi) for weight and activation alike (csrc/x2_common.hpp split8 / mfma_x2), the
     lo lo term dropped, accumulated exactly here (the GPU accumulates in fp32: the quarter of the bound that the
     restatement leaves is for that). An activation the schedule stores in fp16 has no lo half. The depthwise is fp32
     arithmetic on fp32 weights: exact here up to the weights' float32 rounding."""

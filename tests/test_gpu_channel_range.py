@@ -1,7 +1,7 @@
 """GPU: every schedule on weights whose internal channels span 2^KMIN .. 2^KMAX instead of one decade.
 
 With the synthetic weights every stem, expand, depthwise and block output peaks between 2.5 and 10.1, so the fp16
-storage points (fp16, fp16mx) and the hi + lo fp16 operand splits (spef_amd/blob.py split_f16, csrc/k_x2.hip
+storage points (fp16, fp16mx) and the hi + lo fp16 operand splits (spef_amd/blob.py split_f16, csrc/x2_common.hpp
 relu_split8 / split8 / lo_pair) have never seen another magnitude. tests/forward_inputs.py ``rescaled_state_dict``
 scales every internal channel by its own power of two and unscales it at its consumer -- the same function, bit for
 bit in the oracle (tests/test_channel_range_host.py), and the freedom a trained checkpoint has between a BatchNorm

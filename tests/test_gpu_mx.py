@@ -92,7 +92,7 @@ def test_block_outputs_vs_oracle(mx, sd, b, h, w, mx_kernels):
     frames.
 
     mx_kernels = 0 (SPEF_OPT_MX_KERNELS, the library's fallback schedule for the same blob): stem + block 1 and blocks
-    2-4 run on the fp16x2 kernels' fp16-I/O template variants (k_x2.hip IO = 1 / 2 / 3: fp16 input fragments with the
+    2-4 run on the fp16x2 kernels' fp16-I/O template variants (k_x2_irb.hip IO = 1 / 2 / 3: fp16 input fragments with the
     two-MFMA expand, fp16 residual read, fp16 output) with fp32 hidden tensors, so the oracle restates no hidden
     rounding and block 4 is held to the fp32 bound; the fp16 outputs of blocks 1-3 keep the one-step bound."""
     from spef_amd import _lib as L

@@ -1,5 +1,5 @@
-"""GPU: the profiling table names the kernel the library actually launched for each fp16mx block (api_schedule.cpp asks
-k_x2.hip's dispatch table walk, x2_irb_kernel_name), so the bench line's ``roofline.kernel`` and its PMC-traffic lookup
+"""GPU: the profiling table names the kernel the library actually launched for each fp16mx block (api_schedule.cpp labels
+and launches from one plan, x2_plan.hpp's x2_irb_plan), so the bench line's ``roofline.kernel`` and its PMC-traffic lookup
 refer to the real symbol: at the bench workload (B = 64, 512^2) blocks 5-7 run the slab kernel, 8-10 and 14 the
 role-split kernel with persistent tiles, 11-13 and 15-17 the three-stage kernel."""
 import numpy as np

@@ -2,7 +2,7 @@
 what the kernels they replace compute. Every comparison is np.array_equal between option 0 (the earlier kernels) and
 the library default, on the same engine and the same frames.
 
-Bit 0, the last conv's 128-pixel x 320-channel staged tile (k_x2.hip x2_pws_kernel<POOL, X2PwsWide>): the pool form
+Bit 0, the last conv's 128-pixel x 320-channel staged tile (k_x2_pw.hip x2_pws_kernel<POOL, X2PwsWide>): the pool form
 through Engine.forward at M = 192 (a ragged last tile: 64 of its 128 pixels exist), at HW = 192 (128-pixel tiles straddle
 two images) and at HW = 256; the non-pool form through a keypoint-head blob at 240 x 384 (HW = 96, M = 288: the last
 tile has 32 pixels).

@@ -1,4 +1,4 @@
-"""GPU: the fp16x2 schedule (blob dtype 5, csrc/k_x2.hip) -- fp32 activations with hi + lo fp16 MFMA operands, the
+"""GPU: the fp16x2 schedule (blob dtype 5, csrc/k_x2_*.hip) -- fp32 activations with hi + lo fp16 MFMA operands, the
 parity variant for heads the fp16 schedule cannot bound.
 
 Tolerances are the north star's, absolute, with no scaling by the head's weight scale: raw head outputs 1e-3,
