@@ -392,6 +392,38 @@ int spef_refine_keypoints(spef_ctx* ctx, const float* kp, const float* weights, 
                           float* quat_inout, float* pos_inout, float* fit, float* cov, int* iters, int* status,
                           void* stream);
 
+/* Outlier-robust keypoint decode (opt-in; nothing calls it unless asked): exhaustive 3-point consensus between
+ * spef_decode_keypoints and spef_refine_keypoints, on the observations both solve on. A model has n <= 16 points, so
+ * all C(n, 3) <= 560 minimal samples are solved and scored: no sampling, no seed, and a problem's result does not depend
+ * on its batch. Candidates are the points with c_i > 0 (all of them when weights is NULL). Every triple i < j < k of
+ * candidates (index = its rank among all C(n, 3) triples in lexicographic order; a triple whose model triangle is
+ * degenerate is skipped) is solved by P3P in fp64 (Grunert's quartic, closed-form roots + two Newton steps; up to four
+ * poses). A hypothesis is valid when every model point has Z > 0; its cost is the sum over the candidates of
+ * min(e_i^2, inlier_px^2), e_i = reprojection error in pixels. The lowest cost wins (ties: lowest triple, then lowest
+ * root in ascending order); its inliers are the candidates with e_i^2 < inlier_px^2.
+ *   kp        [B x 2(n+1)] normalised keypoints after the sigmoid (spef_decode_keypoints' kp_out).
+ *   weights   NULL or [B x n] confidences c_i >= 0.
+ *   quat_inout / pos_inout  the start pose (EPnP's). On consensus: replaced by the winning hypothesis, the quaternion
+ *             unit and on the start's hemisphere (when the start is finite and nonzero).
+ *   weights_out [B x n]: c_i (or 1) for inliers, 0 otherwise: the weights to hand to spef_refine_keypoints.
+ *   info  [B x 4] (may be NULL): inliers, winning triple index, winning root, hypotheses scored.
+ *   cost  [B] (may be NULL): the winning cost.
+ *   status [B] is ORed into, not cleared: bit 64 = no consensus (a non-finite keypoint or weight, a negative weight,
+ *         fewer than 3 candidates, no valid hypothesis, fewer inliers than min_inliers). The pose is then untouched bit
+ *         for bit, weights_out is the input confidences (or 1), cost is NaN and info is 0, -1, -1, scored. The bit is
+ *         informational, as 16 and 32 are. Bit 8 is not read.
+ * SPEF_ERR_STATE without spef_set_keypoints. SPEF_ERR_ARG, with nothing enqueued: a null required pointer, B < 1,
+ * inlier_px not finite or <= 0, min_inliers outside 4..n. No allocation, no atomics, no host synchronisation. */
+int spef_consensus_keypoints(spef_ctx* ctx, const float* kp, const float* weights, int B, float inlier_px,
+                             int min_inliers, float* quat_inout, float* pos_inout, float* weights_out, int* info,
+                             float* cost, int* status, void* stream);
+/* The same call with one more output: pose64 [B x 12] (may be NULL), the winning hypothesis as it was scored, before the
+ * float32 rounding of quat / pos: R row-major (9), then t (3); NaN on a row with bit 64. A float32 pose reprojects
+ * to about 1e-3 px at best; this one lets a caller verify the minimal solve itself. */
+int spef_consensus_keypoints_f64(spef_ctx* ctx, const float* kp, const float* weights, int B, float inlier_px,
+                                 int min_inliers, float* quat_inout, float* pos_inout, float* weights_out, int* info,
+                                 float* cost, double* pose64, int* status, void* stream);
+
 /* Input preprocessing on the device (SPEDataset.__getitem__ + transforms.Resize(img_size), utils.py:212-249,
  * speed.py:66-69): decoded frames uint8 [B x Hin x Win x 3] (RGB, HWC) -> uint8 [B x H x W x 3], bit-identical to
  * Pillow's Image.resize((W, H), BILINEAR). The result feeds spef_forward with SPEF_IN_U8_NHWC (ToTensor's /255

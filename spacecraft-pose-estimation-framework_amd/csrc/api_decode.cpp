@@ -1,5 +1,6 @@
 // Decode side of the C ABI (include/spef.h): decode tables, the classification / regression decode and the pose
-// covariance of its PDFs, the keypoint model set-up for EPnP and its refinement, and the Pillow-exact resize.
+// covariance of its PDFs, the keypoint model set-up for EPnP, the consensus and the refinement behind it, and the
+// Pillow-exact resize.
 #include <math.h>
 #include <string.h>
 
@@ -308,6 +309,35 @@ int spef_refine_keypoints(spef_ctx* c, const float* kp, const float* weights, in
                          quat_inout, pos_inout, fit, cov, iters, status, s);
   }));
   return SPEF_OK;
+}
+
+int spef_consensus_keypoints_f64(spef_ctx* c, const float* kp, const float* weights, int B, float inlier_px,
+                                 int min_inliers, float* quat_inout, float* pos_inout, float* weights_out, int* info,
+                                 float* cost, double* pose64, int* status, void* stream) {
+  if (!c || !kp || !quat_inout || !pos_inout || !weights_out || !status || B < 1)
+    return fail(SPEF_ERR_ARG, "null argument");
+  if (!(inlier_px > 0.0f) || !std::isfinite(inlier_px)) return fail(SPEF_ERR_ARG, "inlier_px must be finite and > 0");
+  if (!c->kp3d || !c->kp_model) return fail(SPEF_ERR_STATE, "keypoints not configured (spef_set_keypoints)");
+  const int n = c->kp_n;
+  if (min_inliers < 4 || min_inliers > n)
+    return fail(SPEF_ERR_ARG, "min_inliers must be in 4.." + std::to_string(n));
+  Dev d(c->device);
+  hipStream_t s = (hipStream_t)stream;
+  const double triples = n * (n - 1) * (n - 2) / 6.0;
+  HIP_TRY(prof_launch(c, s, "consensus_kernel", (double)B * ((2 * (n + 1) + (weights ? n : 0) + n) * 4 + 2 * 28 + 8 +
+                                                             (info ? 16 : 0) + (cost ? 4 : 0) + (pose64 ? 96 : 0)),
+                      (double)B * triples * (600.0 + 2.0 * (120.0 + 40.0 * n)), [&] {
+    return launch_consensus(kp, weights, B, n, c->kp3d, c->camK, c->cam_nu, c->cam_nv, c->kp_dist, inlier_px,
+                            min_inliers, quat_inout, pos_inout, weights_out, info, cost, pose64, status, s);
+  }));
+  return SPEF_OK;
+}
+
+int spef_consensus_keypoints(spef_ctx* c, const float* kp, const float* weights, int B, float inlier_px,
+                             int min_inliers, float* quat_inout, float* pos_inout, float* weights_out, int* info,
+                             float* cost, int* status, void* stream) {
+  return spef_consensus_keypoints_f64(c, kp, weights, B, inlier_px, min_inliers, quat_inout, pos_inout, weights_out,
+                                      info, cost, nullptr, status, stream);
 }
 
 int spef_preprocess(spef_ctx* c, const uint8_t* frames, int B, int Hin, int Win, uint8_t* out, int H, int W,

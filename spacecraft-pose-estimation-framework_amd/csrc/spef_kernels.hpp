@@ -168,6 +168,15 @@ hipError_t launch_epnp(const float* raw, int B, int n, const float* kp3d, const 
 hipError_t launch_refine(const float* kp, const float* weights, int B, int n, const float* kp3d, const double* K,
                          float nu, float nv, const EpnpDist& dist, int max_iters, float huber_px, float* quat,
                          float* pos, float* fit, float* cov, int* iters, int* status, hipStream_t s);
+// Exhaustive 3-point consensus between EPnP and the refinement (k_consensus.hip): every triple of candidate points
+// (weights > 0; null: all) is solved by P3P and scored on all candidates with min(e^2, inlier_px^2). On consensus quat /
+// pos are replaced by the winning hypothesis and weights_out [B x n] keeps the confidences of its inliers (0 elsewhere);
+// info [B x 4] (inliers, triple, root, hypotheses scored), cost [B] and pose64 [B x 12] (the winning R row-major, then t,
+// before the float32 rounding; NaN without consensus) may be null. status |= 64 (no consensus).
+hipError_t launch_consensus(const float* kp, const float* weights, int B, int n, const float* kp3d, const double* K,
+                            float nu, float nv, const EpnpDist& dist, float inlier_px, int min_inliers, float* quat,
+                            float* pos, float* weights_out, int* info, float* cost, double* pose64, int* status,
+                            hipStream_t s);
 
 // Activation dtype -> fp32 NHWC copy (debug probes / backbone feature export).
 hipError_t launch_to_f32(int dtype, const void* x, float* y, int64_t n, hipStream_t s);

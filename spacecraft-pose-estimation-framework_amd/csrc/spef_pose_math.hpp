@@ -1,5 +1,5 @@
-// fp64 helpers shared by the keypoint decode kernels: the batched EPnP (k_epnp.hip) and the pose refinement behind it
-// (k_refine.hip) -- reciprocal / square root from the hardware estimates, cv::undistortPoints, dcm2quat.
+// fp64 helpers shared by the keypoint decode kernels: the batched EPnP (k_epnp.hip), the 3-point consensus
+// (k_consensus.hip) and the pose refinement (k_refine.hip) behind it -- reciprocal / square root from the hardware estimates, cv::undistortPoints, dcm2quat.
 #pragma once
 
 #include <math.h>

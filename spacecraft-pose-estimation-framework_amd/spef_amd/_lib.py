@@ -76,6 +76,8 @@ SIGNATURES = {
     'spef_set_keypoint_distortion': (_i, [_vp, _vp, _i]),
     'spef_decode_keypoints': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'spef_refine_keypoints': (_i, [_vp, _vp, _vp, _i, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'spef_consensus_keypoints': (_i, [_vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'spef_consensus_keypoints_f64': (_i, [_vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'spef_profile_begin': (_i, [_vp]),
     'spef_profile_end': (_i, [_vp, C.c_char_p, _sz, C.POINTER(_sz)]),
     'spef_measure_peaks': (_i, [_i, _i, C.POINTER(C.c_double)]),

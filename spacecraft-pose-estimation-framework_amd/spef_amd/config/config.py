@@ -23,7 +23,10 @@ DEFAULTS: Dict[str, Any] = {
                  'N_ORI_BINS_PER_DIM': 12, 'N_POS_BINS_PER_DIM': 10, 'ORI_DELETE_UNUSED_BINS': False,
                  'KEYPOINTS_PATH': 'models/3d_models/tangoPoints.mat',
                  # this target: pose refinement behind EPnP (spe/refine.py, csrc/k_refine.hip); 0 trials = off
-                 'KEYPOINTS_REFINE_ITERS': 0, 'KEYPOINTS_REFINE_HUBER_PX': 0.0},
+                 'KEYPOINTS_REFINE_ITERS': 0, 'KEYPOINTS_REFINE_HUBER_PX': 0.0,
+                 # this target: 3-point consensus between EPnP and the refinement (spe/consensus.py,
+                 # csrc/k_consensus.hip); inlier threshold in px, 0 = off; fewest inliers, 0 = max(4, ceil(n / 2))
+                 'KEYPOINTS_CONSENSUS_PX': 0.0, 'KEYPOINTS_CONSENSUS_MIN_INLIERS': 0},
     },
     'DATA': {'BATCH_SIZE': 8, 'PATH': '../datasets/speed', 'IMG_SIZE': (240, 384), 'ORI_SMOOTH_FACTOR': 3,
              'POS_SMOOTH_FACTOR': 100, 'ROT_AUGMENT': True, 'OTHER_AUGMENT': True, 'SHUFFLE': True},
@@ -87,6 +90,7 @@ def load_config(path: str | None = None) -> Config:
         assert h['ORI'] == 'keypoints' and h['POS'] == 'keypoints', \
             "Both ORI and POS must be 'keypoints' if one is 'keypoints'"
     assert 0 <= h['KEYPOINTS_REFINE_ITERS'] <= 100 and h['KEYPOINTS_REFINE_HUBER_PX'] >= 0
+    assert h['KEYPOINTS_CONSENSUS_PX'] >= 0 and h['KEYPOINTS_CONSENSUS_MIN_INLIERS'] in (0, *range(4, 17))
     assert cfg['MI355X']['DTYPE'] in ('fp16mx', 'fp16', 'bf16', 'int8', 'fp32', 'fp16x2')
     assert cfg['MI355X']['CALIB_METHOD'] in ('percentile', 'mse', 'max')
     return _wrap(cfg)
@@ -114,3 +118,12 @@ def keypoint_refine(cfg: Config):
     """``SPEMi355x``'s ``keypoint_refine`` argument from MODEL.HEAD.KEYPOINTS_REFINE_*: (trials, Huber px) or None."""
     h = cfg.MODEL.HEAD
     return (int(h.KEYPOINTS_REFINE_ITERS), float(h.KEYPOINTS_REFINE_HUBER_PX)) if h.KEYPOINTS_REFINE_ITERS else None
+
+
+def keypoint_consensus(cfg: Config):
+    """``SPEMi355x``'s ``keypoint_consensus`` argument from MODEL.HEAD.KEYPOINTS_CONSENSUS_*: (inlier px, fewest inliers
+    or None for the default) or None."""
+    h = cfg.MODEL.HEAD
+    if not h.KEYPOINTS_CONSENSUS_PX:
+        return None
+    return float(h.KEYPOINTS_CONSENSUS_PX), (int(h.KEYPOINTS_CONSENSUS_MIN_INLIERS) or None)

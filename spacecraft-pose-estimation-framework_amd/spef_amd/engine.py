@@ -378,6 +378,7 @@ class Engine:
         self._reserved = (0, 0, 0)
         self._decode_tables = None
         self._kp_refine = None      # (max_iters, huber_px) of set_keypoint_refine, or None: off
+        self._kp_consensus = None   # (inlier_px, min_inliers or None) of set_keypoint_consensus, or None: off
         # bumped by every call that moves device buffers or changes what a recorded forward / decode would do
         # (workspace reallocation, weights, decode tables, options, camera): StreamPipeline's recorded HIP graphs key on it
         self.epoch = 0
@@ -600,15 +601,81 @@ class Engine:
         L.check(self.lib.spef_decode_keypoints(self.ctx, _ptr(raw), B, 1 if apply_sigmoid else 0, _ptr(kp), _ptr(quat),
                                                _ptr(pos), _ptr(status), _stream(dev)))
         dec = {'keypoints': kp, 'ori': quat, 'pos': pos, 'status': status}
-        refine = self._kp_refine
+        refine, weights, q0, t0 = self._kp_refine, None, quat, pos
+        if self._kp_consensus is not None:   # set_keypoint_consensus: inlier selection behind EPnP, same stream
+            con = self.consensus_keypoints(kp, quat, pos, inlier_px=self._kp_consensus[0],
+                                           min_inliers=self._kp_consensus[1], status=status)
+            dec.update(inliers=con['inliers'], n_inliers=con['n_inliers'], ori_consensus=con['ori'],
+                       pos_consensus=con['pos'])
+            weights, q0, t0 = con['weights'], con['ori'], con['pos']
+            if refine is None:               # least squares on the inliers
+                refine = (20, 0.0)
         if refine is not None:   # set_keypoint_refine: Levenberg-Marquardt behind EPnP, same stream
-            ref = self.refine_keypoints(kp, quat, pos, max_iters=refine[0], huber_px=refine[1], status=status,
-                                        want_cov=want_cov)
+            ref = self.refine_keypoints(kp, q0, t0, weights=weights, max_iters=refine[0], huber_px=refine[1],
+                                        status=status, want_cov=want_cov)
             dec.update(ori=ref['ori'], pos=ref['pos'], ori_epnp=quat, pos_epnp=pos, fit=ref['fit'],
                        refine_iters=ref['iters'])
             if want_cov:
                 dec['cov'] = ref['cov']
         return dec
+
+    def set_keypoint_consensus(self, inlier_px=None, min_inliers=None) -> None:
+        """Turn the 3-point consensus between EPnP and the refinement on (``inlier_px``: the inlier threshold in
+        pixels; ``min_inliers``: 4..n, None = max(4, ceil(n / 2))) or off (``inlier_px`` 0 or None, the default).
+        With it on, ``decode_keypoints`` runs EPnP, the consensus and the refinement kernel on one stream: the
+        refinement starts from the consensus pose with the inlier weights, with ``set_keypoint_refine``'s settings
+        when that is on and (20 trials, plain least squares) otherwise. The result gains 'inliers' [B x n] bool,
+        'n_inliers', 'ori_consensus', 'pos_consensus' and the refinement's keys; a row without consensus carries the
+        informational status bit 64 and is EPnP's pose (+ refinement), as with the consensus off."""
+        if not inlier_px:
+            self._kp_consensus = None
+            return
+        inlier_px = float(inlier_px)
+        assert np.isfinite(inlier_px) and inlier_px > 0, 'inlier_px must be finite and > 0'
+        assert min_inliers is None or int(min_inliers) >= 4, 'min_inliers must be in 4..n'
+        self._kp_consensus = (inlier_px, None if min_inliers is None else int(min_inliers))
+
+    def consensus_keypoints(self, kp: torch.Tensor, quat: torch.Tensor, pos: torch.Tensor, weights=None,
+                            inlier_px: float = 8.0, min_inliers=None, status=None, want_pose64: bool = False) -> dict:
+        """Exhaustive 3-point consensus (csrc/k_consensus.hip; ``spe.consensus.consensus_host`` is its NumPy twin)
+        on the normalised keypoints ``kp`` [B x 2(n+1)] (after the sigmoid) from the start pose ``quat`` / ``pos``
+        (EPnP's), with optional confidences ``weights`` [B x n] (points with 0 are neither sampled nor scored). The
+        inputs are left as they are. -> {'ori', 'pos' (the winning hypothesis; the start pose on a row without
+        consensus), 'inliers' [B x n] bool, 'weights' [B x n] (the confidences of the inliers, 0 elsewhere: what
+        ``refine_keypoints`` takes), 'n_inliers', 'triple', 'root', 'scored' [B] int32, 'cost' [B], 'status'}.
+        ``status`` [B] int32, when given, is ORed into in place: bit 64 = no consensus. ``want_pose64`` adds 'R'
+        [B x 3 x 3] and 't' [B x 3], the winning hypothesis in float64 as it was scored (NaN without consensus)."""
+        B = kp.shape[0]
+        dev = self.device
+        assert kp.dtype == torch.float32 and kp.is_contiguous() and kp.dim() == 2
+        n = kp.shape[1] // 2 - 1
+        q = quat.detach().to(dev, torch.float32).reshape(B, 4).clone()
+        t = pos.detach().to(dev, torch.float32).reshape(B, 3).clone()
+        w = None
+        if weights is not None:
+            w = weights.detach().to(dev, torch.float32).contiguous()
+            assert w.dim() == 2 and w.shape[0] == B and w.shape[1] == n
+        if min_inliers is None:
+            min_inliers = max(4, (n + 1) // 2)
+        wout = torch.empty((B, n), dtype=torch.float32, device=dev)
+        info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        cost = torch.empty((B,), dtype=torch.float32, device=dev)
+        if status is None:
+            status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() == B
+        p64 = torch.empty((B, 12), dtype=torch.float64, device=dev) if want_pose64 else None
+        if want_pose64:
+            L.check(self.lib.spef_consensus_keypoints_f64(self.ctx, _ptr(kp), _ptr(w), B, float(inlier_px),
+                                                          int(min_inliers), _ptr(q), _ptr(t), _ptr(wout), _ptr(info),
+                                                          _ptr(cost), _ptr(p64), _ptr(status), _stream(dev)))
+        else:
+            L.check(self.lib.spef_consensus_keypoints(self.ctx, _ptr(kp), _ptr(w), B, float(inlier_px),
+                                                      int(min_inliers), _ptr(q), _ptr(t), _ptr(wout), _ptr(info),
+                                                      _ptr(cost), _ptr(status), _stream(dev)))
+        extra = {'R': p64[:, :9].reshape(B, 3, 3), 't': p64[:, 9:]} if want_pose64 else {}
+        return {**extra, 'ori': q, 'pos': t, 'inliers': (wout > 0) & (info[:, 1:2] >= 0), 'weights': wout,
+                'n_inliers': info[:, 0], 'triple': info[:, 1], 'root': info[:, 2], 'scored': info[:, 3], 'cost': cost,
+                'status': status}
 
     def set_keypoint_refine(self, max_iters=None, huber_px: float = 0.0) -> None:
         """Turn the pose refinement behind EPnP on (``max_iters`` trials in 1..100, Huber threshold ``huber_px`` in

@@ -219,6 +219,12 @@ class StreamPipeline:
         for e in self.engines:
             e.set_keypoint_refine(max_iters, huber_px)
 
+    def set_keypoint_consensus(self, inlier_px=None, min_inliers=None) -> None:
+        """``Engine.set_keypoint_consensus`` on every slot: ``submit_keypoints`` then runs the 3-point consensus
+        between EPnP and the refinement. ``inlier_px`` 0 or None turns it off."""
+        for e in self.engines:
+            e.set_keypoint_consensus(inlier_px, min_inliers)
+
     def submit_keypoints(self, frames: torch.Tensor, score=None, track=None) -> dict:
         """Keypoint mode: forward (KeypointRegressionHead) + sigmoid + batched EPnP (+ the pose refinement, when
         ``set_keypoint_refine`` turned it on) of one batch on the next stream; returns the decode dict of

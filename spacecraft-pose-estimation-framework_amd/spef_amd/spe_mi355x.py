@@ -37,12 +37,21 @@ class SPEMi355x:
         keypoint_refine: None (off) or ``(max_iters, huber_px)``: keypoint mode refines EPnP's pose by robust
             Levenberg-Marquardt on the GPU (``Engine.set_keypoint_refine``); ``predict`` then returns the refined
             'ori' / 'pos' and adds 'ori_epnp', 'pos_epnp' and 'reproj_rms' (px, before / after).
+        keypoint_consensus: None (off) or ``(inlier_px, min_inliers)`` (``min_inliers`` 0 or None: the default,
+            max(4, ceil(n / 2))): keypoint mode selects inliers by exhaustive 3-point consensus between EPnP and the
+            refinement (``Engine.set_keypoint_consensus``); ``predict`` then also returns 'inliers', 'n_inliers',
+            'ori_consensus' and 'pos_consensus'.
     """
 
     def __init__(self, model: Union[bytes, str, Engine], device: Union[str, torch.device], spe_utils,
-                 keypoint_refine=None) -> None:
+                 keypoint_refine=None, keypoint_consensus=None) -> None:
         self.spe_utils = spe_utils
         self.keypoint_refine = tuple(keypoint_refine) if keypoint_refine and keypoint_refine[0] else None
+        self.keypoint_consensus = None
+        if keypoint_consensus and keypoint_consensus[0]:
+            self.keypoint_consensus = (float(keypoint_consensus[0]),
+                                       int(keypoint_consensus[1]) if len(keypoint_consensus) > 1 and
+                                       keypoint_consensus[1] else None)
         self.device = torch.device(device)
         self.engine = None
         self._video = None          # (configuration, VideoFilter) of predict_video
@@ -78,6 +87,8 @@ class SPEMi355x:
                 raise AssertionError(f'keypoint head width {self.engine.n_out0} != 2 * (n_keypoints + 1)')
             if self.keypoint_refine is not None:
                 self.engine.set_keypoint_refine(*self.keypoint_refine)
+            if self.keypoint_consensus is not None:
+                self.engine.set_keypoint_consensus(*self.keypoint_consensus)
             return
         ori_bins = su.orientation.histogram if self.ori_mode == L.CLASSIFICATION else None
         pos_grid = su.position.histogram if self.pos_mode == L.CLASSIFICATION else None
@@ -178,6 +189,8 @@ class SPEMi355x:
                 self._pipe.set_keypoints(kp, kk.reshape(3, 3), float(cam.nu), float(cam.nv), dd if dd.size else None)
                 if self.keypoint_refine is not None:
                     self._pipe.set_keypoint_refine(*self.keypoint_refine)
+                if self.keypoint_consensus is not None:
+                    self._pipe.set_keypoint_consensus(*self.keypoint_consensus)
         return self._pipe
 
     def _close_pipe(self) -> None:
@@ -248,7 +261,8 @@ class SPEMi355x:
         pose is what ``predict`` returns, except that a row whose decode failed does not raise here: the tracker coasts
         over it and reports it in ``tracked['track_status']`` (bit 1; with bit 8 when the stream has no track yet and the
         row passes through). The tracked pose has 'ori', 'pos', 'mahalanobis' and 'track_status'. In keypoint mode with
-        ``keypoint_refine`` the refined pose's covariance is the measurement covariance. Behind the URSONet heads
+        ``keypoint_refine`` or ``keypoint_consensus`` the refined pose's covariance (which counts the inliers only) is the
+        measurement covariance. Behind the URSONet heads
         ``pdf_cov=True`` makes it the covariance of the soft-classification PDFs about their own decode
         (``Engine.decode_cov`` with ``fixed_var`` = the tracker's ``r`` for a regression head and ``floor_var`` added to
         a classification head's diagonal; a row whose PDF gives no covariance falls back to ``r``), which lets a
@@ -268,7 +282,8 @@ class SPEMi355x:
         start.record()
         raw0, raw1 = self.engine.forward(x)
         if self.keypoint_mode:
-            dec = self.engine.decode_keypoints(raw0, apply_sigmoid=True, want_cov=self.keypoint_refine is not None)
+            dec = self.engine.decode_keypoints(raw0, apply_sigmoid=True, want_cov=self.keypoint_refine is not None or
+                                               self.keypoint_consensus is not None)
         elif pdf_cov:
             dec = self.engine.decode(self.ori_mode, self.pos_mode, raw0, raw1, want_cov=True, fixed_var=trk.params['r'],
                                      floor_var=floor_var)
@@ -297,7 +312,8 @@ class SPEMi355x:
         if np.any(status & 8):
             raise ValueError('EPnP failed on a batch row (degenerate keypoints)')   # cv2.solvePnP error analogue
 
-        # bits 16 (row not refined) and 32 (refinement stopped at max_iters) are informational: the pose stands
+        # bits 16 (row not refined), 32 (refinement stopped at max_iters) and 64 (no consensus) are informational: the
+        # pose stands
         if self.keypoint_mode:
             pose = {'keypoints': dec['keypoints'].cpu().numpy(), 'ori': dec['ori'].cpu().numpy(),
                     'pos': dec['pos'].cpu().numpy()}
@@ -305,6 +321,9 @@ class SPEMi355x:
                 pose['ori_epnp'] = dec['ori_epnp'].cpu().numpy()
                 pose['pos_epnp'] = dec['pos_epnp'].cpu().numpy()
                 pose['reproj_rms'] = dec['fit'][:, :2].cpu().numpy()
+            for k in ('inliers', 'n_inliers', 'ori_consensus', 'pos_consensus'):   # keypoint_consensus
+                if k in dec:
+                    pose[k] = dec[k].cpu().numpy()
             if want_cov and 'cov' in dec:
                 pose['cov'] = dec['cov'].cpu().numpy()
             return pose

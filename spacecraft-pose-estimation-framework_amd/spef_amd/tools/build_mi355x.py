@@ -87,7 +87,7 @@ def evaluate_variants(sd, cfg, arch, out_dir: str, variants, calib_frames=None, 
     latter. ``reference``: optional callable, float32 NCHW [0,1] images -> (ori, pos) raw head outputs."""
     import numpy as np
     import torch
-    from ..config import keypoint_refine, to_spe_utils
+    from ..config import keypoint_consensus, keypoint_refine, to_spe_utils
     from ..data.synthetic import speed_like_loader
     from ..spe_mi355x import SPEMi355x
     from .compare import feature_stats
@@ -103,7 +103,8 @@ def evaluate_variants(sd, cfg, arch, out_dir: str, variants, calib_frames=None, 
     outs, poses, summary = {}, {}, {'frames': int(B * n_batches), 'img_size': list(size), 'variants': {}}
     for v in variants:
         blob, _ = pack_variant(sd, cfg, arch, v, calib_frames, bit_width)
-        spe = SPEMi355x(blob, dev, su, keypoint_refine=keypoint_refine(cfg))
+        spe = SPEMi355x(blob, dev, su, keypoint_refine=keypoint_refine(cfg),
+                        keypoint_consensus=keypoint_consensus(cfg))
         try:
             score, error = evaluation(spe, {'synthetic': batches}, su, ('synthetic',))
             with open(os.path.join(ed, f'eval_{v}.json'), 'w') as f:

@@ -25,7 +25,7 @@ def main(argv=None):
                     help='score on the device (evaluation_device) instead of the per-batch host loop')
     a = ap.parse_args(argv)
     import torch
-    from ..config import keypoint_refine, load_config, to_spe_utils
+    from ..config import keypoint_consensus, keypoint_refine, load_config, to_spe_utils
     from ..data.synthetic import speed_like_loader
     from ..spe.camera import CAMERAS
     from ..spe_mi355x import SPEMi355x
@@ -35,7 +35,8 @@ def main(argv=None):
     dev = torch.device(f'cuda:{cfg.MI355X.DEVICE}')
     camera = CAMERAS['speed_plus' if 'plus' in cfg.DATA.PATH else 'speed']
     su = to_spe_utils(cfg, camera)
-    spe = SPEMi355x(os.path.join(a.build, 'model.spef'), dev, su, keypoint_refine=keypoint_refine(cfg))
+    spe = SPEMi355x(os.path.join(a.build, 'model.spef'), dev, su, keypoint_refine=keypoint_refine(cfg),
+                    keypoint_consensus=keypoint_consensus(cfg))
     B, size = cfg.MI355X.BATCH_SIZE, tuple(cfg.DATA.IMG_SIZE)
 
     if a.data:

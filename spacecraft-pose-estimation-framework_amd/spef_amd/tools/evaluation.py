@@ -4,7 +4,9 @@ per-image errors) -- driving any object with ``predict(images) -> (pose, latency
 
 Keypoint mode with MODEL.HEAD.KEYPOINTS_REFINE_ITERS > 0 (``SPEMi355x(..., keypoint_refine=config.keypoint_refine(cfg))``)
 scores the pose refined behind EPnP in both loops: ``predict`` returns it, and ``eval_pipeline`` configures every slot
-of the device loop's ``StreamPipeline`` with it."""
+of the device loop's ``StreamPipeline`` with it. MODEL.HEAD.KEYPOINTS_CONSENSUS_PX > 0
+(``keypoint_consensus=config.keypoint_consensus(cfg)``) puts the 3-point consensus in front of that refinement in the same
+way: the scored pose is the one refined on the inliers."""
 from __future__ import annotations
 
 from typing import Any, Dict, Iterable, Tuple
