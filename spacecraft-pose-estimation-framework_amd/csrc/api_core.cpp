@@ -97,6 +97,7 @@ static const OptionDesc kOptions[] = {
     {SPEF_OPT_Q8_ROLESPLIT, &spef_ctx::q8_rolesplit, false, 0, 1, "SPEF_OPT_Q8_ROLESPLIT: 0 or 1"},
     {SPEF_OPT_MX_KERNELS, &spef_ctx::mx_kernels, true, 0, 0, nullptr},
     {SPEF_OPT_TRIM, &spef_ctx::trim, false, 0, 3, "SPEF_OPT_TRIM: bits 0-1"},
+    {SPEF_OPT_X2_STAGE, &spef_ctx::x2_stage, false, 0, 1, "SPEF_OPT_X2_STAGE: 0 or 1"},
     {SPEF_OPT_WAVESPEC, &spef_ctx::wavespec, false, 0, 2, "SPEF_OPT_WAVESPEC: 0, 1 or 2"},
 };
 

@@ -230,7 +230,7 @@ int irb_step_x2(const Run& r, const OpDesc& op, const Block& g, Act& a) {
       return launch_mx_irb(g.cin, g.hid, g.cout, g.stride, g.res, cur16, o16, x, wt.w0, wt.b0, (const float*)wt.w1,
                            wt.b1, wt.w2, wt.b2, y, B, h, w, OH, OW, s, mxlean);
     return launch_x2_irb(blk, plan, {x, wt.w0, wt.b0, (const float*)wt.w1, wt.b1, wt.w2, wt.b2, y, B, h, w, OH, OW,
-                                     scratch, io, cus}, s);
+                                     scratch, io, cus, c->x2_stage}, s);
   }));
   advance(a, y, OH, OW, op.cout, o16);
   return SPEF_OK;

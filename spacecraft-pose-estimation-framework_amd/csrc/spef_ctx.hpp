@@ -64,6 +64,7 @@ struct spef_ctx {
   int mx_kernels = 1;        // SPEF_OPT_MX_KERNELS (spef_tuning.hpp): fp16mx blocks 2-7 on k_mx.hip
   int trim = 3;              // SPEF_OPT_TRIM (spef_tuning.hpp): bit 0 = the last conv's 128 x 320 tile, bit 1 = the
                              // lean tile set-up of mx_irb_kernel
+  int x2_stage = 1;          // SPEF_OPT_X2_STAGE (spef_tuning.hpp): blocks 8-10 / 14 on x2_irw_st_kernel (static staging)
   // int8 blob: host copies of the FC quantisation constants, and their per-map-size device forms
   std::vector<double> q8_sw, q8_bias;
   std::vector<int32_t> q8_wsum;

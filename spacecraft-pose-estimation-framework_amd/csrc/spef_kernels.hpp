@@ -108,6 +108,7 @@ struct X2Args {
   int B, H, W, OH, OW;
   float* scratch;
   int io, num_cu;
+  int stage = 1;   // SPEF_OPT_X2_STAGE: the persistent role-split rows (kind 3) on x2_irw_st_kernel (0: x2_irw_kernel)
 };
 // Runs the plan's row (hipErrorNotSupported when the plan found none); the plan must come from x2_irb_plan with
 // this block, a.B, a.OH, a.OW, a.scratch != nullptr, a.io and a.num_cu.

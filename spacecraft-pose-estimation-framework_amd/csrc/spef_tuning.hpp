@@ -17,6 +17,11 @@
 //                         per-pixel addresses (a map too large for the offsets runs the earlier form whatever the bit,
 //                         under the profile key mx_irb_kernel_wide). Default 3 (all bits); a cleared bit runs the
 //                         earlier kernel from the same build.
+//   SPEF_OPT_X2_STAGE   : how the persistent role-split rows of the fp16x2 / fp16mx schedules (x2_plan.hpp kind 3:
+//                         blocks 8-10 and 14) stage a chunk's weights. 1 (default): x2_irw_st_kernel -- every stage piece
+//                         by LDS-DMA into static, separately named double buffers, kept in flight across the chunk
+//                         barrier. 0: x2_irw_kernel -- register staging (blocks 8-10) / LDS-DMA into one dynamic array,
+//                         drained every chunk (block 14). Bit-identical outputs, same plan and profile keys.
 #pragma once
 
 enum spef_tuning_option {
@@ -25,5 +30,6 @@ enum spef_tuning_option {
   SPEF_OPT_IRB_VARIANT = 4,
   SPEF_OPT_TEST_FAIL_BCAST = 5,
   SPEF_OPT_MX_KERNELS = 8,
-  SPEF_OPT_TRIM = 9
+  SPEF_OPT_TRIM = 9,
+  SPEF_OPT_X2_STAGE = 10
 };

@@ -19,7 +19,8 @@
 //                  back from L2) -> fp32 block output. Block 1 (t = 1) stages its input straight into the slab.
 //                  (k_x2_irb.hip)
 //   x2_irw_kernel  the same block, role-split into expand and depthwise/project waves with LDS-staged weights (blocks
-//                  8-17, k_x2_irw.hip); x2_irp_kernel, its three-stage form (k_x2_irp.hip).
+//                  8-17, k_x2_irw.hip; x2_irw_st_kernel there: the same with LDS-DMA staging kept in flight, the
+//                  persistent-tile blocks 8-10 and 14); x2_irp_kernel, its three-stage form (k_x2_irp.hip).
 //   x2_front_kernel  uint8 frames -> stem + block 1 (k_x2_front.hip).
 //   x2_pw_kernel   1x1 conv on fp32 activations (the last ConvBnAct 320 -> 1280, mobilenet_v2.py:264): B fragments
 //                  split on load, ReLU, fp32 output (the keypoint head's flatten input or the URSONet mean's)

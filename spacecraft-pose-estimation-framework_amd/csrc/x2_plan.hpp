@@ -22,6 +22,10 @@ namespace spef {
 // (x2_irp_kernel) without / with persistent tiles. Measured per step at B = 64 (tools/ktime.sh, bit-identical
 // outputs): blocks 15-16 131.4 -> 101.9 us on kind 5, blocks 12-13 147.9 -> 142.0 and block 11 51.8 -> 49.1 on kind
 // 6; blocks 8-10 130.7 -> 138.5 on kind 6 (their VALU role is the longer one there), so they stay on kind 3.
+// Kind 3 launches x2_irw_st_kernel (the role-split kernel with the three-stage kernel's staging: LDS-DMA into static
+// double buffers, in flight across the chunk barrier) unless SPEF_OPT_X2_STAGE is 0; same row, same profile key.
+// Interleaved on one engine at B = 64 (tools/trim_ab.py 0 1 6 10): blocks 8-10 126.7-127.8 -> 114.0-114.6 us per step,
+// block 14 63.6-64.1 -> 54.4-54.7.
 #define SPEF_X2_MID(X)                                           \
   X(64, 384, 64, 1, true, true, 8, 16, 8, 1, 3)      /* 8-10 */   \
   X(64, 384, 96, 1, true, false, 8, 16, 8, 1, 6)     /* 11 */     \

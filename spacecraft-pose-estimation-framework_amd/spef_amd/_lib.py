@@ -21,6 +21,8 @@ OPT_MX_KERNELS = 8   # internal: fp16mx blocks 2-7 on k_mx.hip (1) or the fp16x2
 OPT_TRIM = 9         # internal, one bit per kernel (a cleared bit runs the earlier kernel): bit 0 = the last conv's
 #                      128 x 320 tile (0: 64 x 256), bit 1 = mx_irb_kernel's lean tile set-up (0: 64-bit addresses)
 OPT_TRIM_DEFAULT = 3
+OPT_X2_STAGE = 10    # internal: blocks 8-10 / 14 on x2_irw_st_kernel (1, default: static LDS-DMA staging) or x2_irw_kernel (0)
+OPT_X2_STAGE_DEFAULT = 1
 
 # name -> (restype, argtypes); keep in sync with include/spef.h (tests/test_abi.py checks the header)
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t

@@ -4,7 +4,9 @@ writes them over its output; Engine.probe returns that output. Slots per chunk: 
 2 after the stage stores (register staging only), 1 before the barrier; depthwise wave 4 -- 4 loop start, 5 after the
 depthwise (before the project MFMAs), 6 before the barrier; slot 3 of chunks 0 / 1: expand wave 0 at kernel entry /
 after the input fragments; slot 7 of chunks 1 / 0: depthwise wave 4 at kernel entry / after the epilogue stores.
-Outputs are wrong by construction."""
+x2_irw_st_kernel (SPEF_OPT_X2_STAGE = 1) stamps the same slots; its slot 2 is taken after the LDS-DMA issue.
+KSTAMP_OPS=8,14 picks the blocks (role-split ones: the three-stage blocks are tools/kstamp_irp.py's), KSTAMP_OPT=10=0
+sets a tuning option first. Outputs are wrong by construction."""
 import os
 import sys
 
@@ -24,7 +26,11 @@ for _ in range(3):
     eng.forward(fr)
 torch.cuda.synchronize()
 PT = int(os.environ.get('KSTAMP_TILES', '2'))   # tiles per workgroup of the persistent blocks (8-14) at B = 64
-for op, nch1 in ((8, 12), (12, 18), (15, 30), (17, 30)):
+NCH = {8: 12, 12: 18, 14: 18, 15: 30, 17: 30}   # hidden chunks per tile
+if os.environ.get('KSTAMP_OPT'):
+    eng.set_option(*(int(v) for v in os.environ['KSTAMP_OPT'].split('=')))
+for op in (int(v) for v in os.environ.get('KSTAMP_OPS', '8,14').split(',')):
+    nch1 = NCH[op]
     nch = nch1 * (PT if op < 15 else 1)
     eng.probe(fr, op)
     y = eng.probe(fr, op)
@@ -36,7 +42,7 @@ for op, nch1 in ((8, 12), (12, 18), (15, 30), (17, 30)):
     d_dw = (st[:, 5] - st[:, 4])
     d_busy = (st[:, 6] - st[:, 4])
     print(f'block {op}: {nch} chunks, total {st[-1, 1] - t0} cycles; per chunk (median): period {int(np.median(per))}, '
-          f'expand start->barrier {int(np.median(e_busy))}, stage stores {int(np.median(st[:, 2] - st[:, 0])) if st[0, 2] else "-"}, '
+          f'expand start->barrier {int(np.median(e_busy))}, stage stores / DMA issue {int(np.median(st[:, 2] - st[:, 0])) if st[0, 2] else "-"}, '
           f'dw start->depthwise done {int(np.median(d_dw))}, dw start->barrier {int(np.median(d_busy))}')
     e0 = st[0, 3]
     print(f'   entry->fragments {st[1, 3] - e0}, entry->loop start {t0 - e0}, last prebar->epilogue done '
