@@ -144,6 +144,35 @@ int spef_decode_cov(spef_ctx* ctx, int ori_mode, int pos_mode, const float* ori_
                     int n_pos, const float* quat, const float* pos, int B, const spef_cov_params* params, float* cov,
                     float* ori_hinv, int* cov_status, void* stream);
 
+/* Multi-hypothesis orientation decode (opt-in; nothing calls it unless asked): up to k_max orientations that the
+ * soft-classification PDF holds at once, where spef_decode returns their one Markley average (an ambiguous view puts
+ * two or more peaks into the PDF; their average is none of them). spef_amd/spe/modes.py is the NumPy twin and states
+ * every step; DESIGN.md section 3, Modes path. Works on spef_decode's ori_soft or spef_video_step's ori_filt. All
+ * arithmetic is fp64, every sum in a fixed order: a row's result does not depend on the batch it is in.
+ *
+ * Per row, with c = cos(sep_deg / 2) and |a . b| the absolute 4-D dot product: seeds by greedy suppression (the alive bin
+ * of largest p, float32 values compared exactly, ties to the lowest index; a bin is alive while |q_j . q_s| < c for every
+ * seed so far; stop at p <= 0 or, after the first, at p < seed_rel * p_seed0), `rounds` Lloyd rounds (a bin goes to the
+ * mode of largest |q_i . m_k|, ties to the lowest k; m_k = the Markley average of its cluster), a prune by descending
+ * mass (drop a mode of mass < min_mass, or within sep_deg of one already kept), and a final assignment over the
+ * survivors.
+ * spef_modes_params: k_max in 1..SPEF_MODES_MAX, rounds in 0..8, 0 < sep_deg <= 180, seed_rel in [0, 1], min_mass in
+ *   [0, 1 / k_max], floor_var >= 0 (added to the diagonal of every theta block), all finite (SPEF_ERR_ARG otherwise).
+ * mode_quat [B x k_max x 4]  unit quaternions, scalar part >= 0, by descending mass; mode_mass [B x k_max] the
+ *   clusters' shares of sum p; mode_cov [B x k_max x 9] the theta block of spef_decode_cov restricted to the
+ *   cluster's bins, about its mode, row-major 3 x 3. Entries at or past n_modes[b] are NaN. With one mode the result is
+ *   the plain Markley decode of the whole PDF, mass 1, and spef_decode_cov's theta block.
+ * n_modes [B]: 1..k_max, 0 for an invalid row. modes_status [B] (a word of its own, never ORed into the decode status):
+ *   1 = the PDF is not finite or sum p is not positive and finite; every output of the row is NaN.
+ * n_ori must equal the table's bin count (SPEF_ERR_ARG); SPEF_ERR_STATE without an orientation table; SPEF_ERR_ARG, with
+ * nothing enqueued, also for a NULL pointer and B < 1. One launch, one workgroup per row; no atomics, no allocation and
+ * no host synchronisation: it can follow spef_decode on a stream and be stream-captured. */
+#define SPEF_MODES_MAX 4
+typedef struct { int k_max, rounds; double sep_deg, seed_rel, min_mass, floor_var; } spef_modes_params;
+int spef_decode_modes(spef_ctx* ctx, const float* ori_pdf, int n_ori, int B, const spef_modes_params* params,
+                      float* mode_quat, float* mode_mass, float* mode_cov, int* n_modes, int* modes_status,
+                      void* stream);
+
 /* Adaptive video filter on the device: the reference's TemporalPDF.update_pdf (src/temporal/pdf_compare.py:94-134)
  * and the quaternion pole continuity of Inference.predict (src/temporal/inference.py:136-144, :173-180) for batches
  * of video frames. Frames are TIME-MAJOR: a batch of T * S rows holds T consecutive time steps of S independent
@@ -309,6 +338,23 @@ int spef_track_set_state(spef_track* track, int first_stream, int n, const doubl
 int spef_track_step(spef_track* track, const float* quat, const float* pos, const float* cov, const int* status,
                     int T, int S, float* quat_out, float* pos_out, float* d2, float* cov_out, float* rates_out,
                     int* track_status, void* stream_hip);
+/* spef_track_step with up to K (1..SPEF_MODES_MAX) orientation candidates per row, the outputs of spef_decode_modes
+ * (K = its k_max): the tracker resolves the ambiguity by temporal association. mode_quat [T*S x K x 4], mode_mass
+ * [T*S x K], mode_cov [T*S x K x 9], n_modes [T*S]; pos [T*S x 3] and cov [T*S x 36] (required: spef_decode_cov's
+ * output, which supplies the t block) are shared by a row's candidates. Candidate k < n_modes is valid when its
+ * quaternion is finite and non-zero and its mass is finite and > 0; its covariance C_k is cov with the block
+ * [0:3, 0:3] replaced by mode_cov[k], then treated as spef_track_step treats cov. With a track the candidate of
+ * smallest cost_k = d2_k + 2 sum_j ln L_k[j][j] - 2 ln mass_k (twice the negative log-likelihood of the innovation
+ * under S_k = P-[0:6, 0:6] + R_k = L_k L_k^T, weighted by the mass; a failed pivot makes the candidate invalid; ties to
+ * the lowest k) is the measurement; without a track the lowest valid k (the heaviest mode) is. With no valid candidate
+ * the measurement is invalid. Everything else -- gating on the chosen d2, coasting, the update, the outputs -- is
+ * spef_track_step's; with K = 1 the two agree bit for bit. chosen [T*S]: the index of the candidate taken, -1 when
+ * none. A row that passes through (track_status 1 | 8) returns candidate 0 as it came. Both steps may be mixed on one
+ * tracker. SPEF_ERR_ARG, with nothing enqueued, for a NULL required pointer, K out of range, S or T as above. */
+int spef_track_step_modes(spef_track* track, const float* mode_quat, const float* mode_mass, const float* mode_cov,
+                          const int* n_modes, int K, const float* pos, const float* cov, const int* status, int T,
+                          int S, float* quat_out, float* pos_out, float* d2, float* cov_out, float* rates_out,
+                          int* track_status, int* chosen, void* stream_hip);
 int spef_track_destroy(spef_track* track);
 
 /* Histogram observers for the INT8 calibration: the statistic of every activation-quantizer input of the float model,

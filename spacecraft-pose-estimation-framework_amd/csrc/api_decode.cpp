@@ -149,6 +149,46 @@ int spef_decode_cov(spef_ctx* c, int ori_mode, int pos_mode, const float* ori_pd
   return SPEF_OK;
 }
 
+int spef_decode_modes(spef_ctx* c, const float* ori_pdf, int n_ori, int B, const spef_modes_params* prm,
+                      float* mode_quat, float* mode_mass, float* mode_cov, int* n_modes, int* modes_status,
+                      void* stream) {
+  if (!c) return fail(SPEF_ERR_ARG, "null context");
+  if (B < 1 || !ori_pdf || !prm || !mode_quat || !mode_mass || !mode_cov || !n_modes || !modes_status)
+    return fail(SPEF_ERR_ARG, "null argument");
+  if (prm->k_max < 1 || prm->k_max > SPEF_MODES_MAX)
+    return fail(SPEF_ERR_ARG, "k_max must be in 1.." + std::to_string(SPEF_MODES_MAX));
+  if (prm->rounds < 0 || prm->rounds > 8) return fail(SPEF_ERR_ARG, "rounds must be in 0..8");
+  if (!std::isfinite(prm->sep_deg) || !std::isfinite(prm->seed_rel) || !std::isfinite(prm->min_mass) ||
+      !std::isfinite(prm->floor_var))
+    return fail(SPEF_ERR_ARG, "the modes parameters must be finite");
+  if (!(prm->sep_deg > 0.0 && prm->sep_deg <= 180.0)) return fail(SPEF_ERR_ARG, "sep_deg must be in (0, 180]");
+  if (!(prm->seed_rel >= 0.0 && prm->seed_rel <= 1.0)) return fail(SPEF_ERR_ARG, "seed_rel must be in [0, 1]");
+  if (!(prm->min_mass >= 0.0 && prm->min_mass <= 1.0 / prm->k_max))
+    return fail(SPEF_ERR_ARG, "min_mass must be in [0, 1 / k_max]");
+  if (!(prm->floor_var >= 0.0)) return fail(SPEF_ERR_ARG, "floor_var must be >= 0");
+  if (!c->d_ori_bins) return fail(SPEF_ERR_STATE, "orientation bins not set (spef_set_decode_tables)");
+  if (n_ori != c->n_ori_bins)
+    return fail(SPEF_ERR_ARG, "the orientation PDF is " + std::to_string(n_ori) + " wide, the histogram has " +
+                                  std::to_string(c->n_ori_bins) + " bins");
+  Dev d(c->device);
+  hipStream_t s = (hipStream_t)stream;
+  ModesParams p;
+  p.k_max = prm->k_max;
+  p.rounds = prm->rounds;
+  p.cos_half_sep = cos(prm->sep_deg * (M_PI / 180.0) * 0.5);
+  p.seed_rel = prm->seed_rel;
+  p.min_mass = prm->min_mass;
+  p.floor_var = prm->floor_var;
+  // passes over the row: sum p, <= k_max seedings, `rounds` + 1 moment passes, the prune's masses, the theta blocks
+  const double passes = 3.0 + p.k_max + p.rounds;
+  HIP_TRY(prof_launch(c, s, "decode_modes_kernel", (double)B * (4.0 * n_ori + 14.0 * 4 * p.k_max + 8.0) + 32.0 * n_ori,
+                      (double)B * n_ori * (passes * 30.0 * p.k_max + 120.0), [&] {
+    return launch_decode_modes(ori_pdf, n_ori, c->d_ori_bins, B, p, mode_quat, mode_mass, mode_cov, n_modes,
+                               modes_status, s);
+  }));
+  return SPEF_OK;
+}
+
 int spef_set_keypoints(spef_ctx* c, const float* kp3d, int n, const double* K, float nu, float nv) {
   if (!c || !kp3d || !K || n < 4 || n > 16) return fail(SPEF_ERR_ARG, "bad keypoint configuration");
   // All or nothing: the model is computed and checked on the host and both device buffers are allocated and filled

@@ -439,4 +439,31 @@ int spef_track_step(spef_track* tr, const float* quat, const float* pos, const f
   return SPEF_OK;
 }
 
+int spef_track_step_modes(spef_track* tr, const float* mode_quat, const float* mode_mass, const float* mode_cov,
+                          const int* n_modes, int K, const float* pos, const float* cov, const int* status, int T,
+                          int S, float* quat_out, float* pos_out, float* d2, float* cov_out, float* rates_out,
+                          int* track_status, int* chosen, void* stream_hip) {
+  if (!tr) return fail(SPEF_ERR_ARG, "null tracker");
+  if (!mode_quat || !mode_mass || !mode_cov || !n_modes || !pos || !cov || !quat_out || !pos_out || !track_status ||
+      !chosen)
+    return fail(SPEF_ERR_ARG, "null argument");
+  if (K < 1 || K > SPEF_MODES_MAX) return fail(SPEF_ERR_ARG, "K must be in 1.." + std::to_string(SPEF_MODES_MAX));
+  if (S != tr->S)
+    return fail(SPEF_ERR_ARG, "S = " + std::to_string(S) + ", the tracker has " + std::to_string(tr->S) + " streams");
+  if (T < 1) return fail(SPEF_ERR_ARG, "T must be at least 1");
+  if ((int64_t)T * S * 36 > 0x7fffffff) return fail(SPEF_ERR_ARG, "too many rows");
+  spef_ctx* c = tr->ctx;
+  Dev d(tr->device);
+  hipStream_t s = (hipStream_t)stream_hip;
+  const double rows = (double)T * S;
+  HIP_TRY(prof_launch(c, s, "track_step_modes_kernel",
+                      rows * (K * 56 + 4 + 12 + 28 + 12 + 144 + (status ? 4 : 0) + (cov_out ? 144 : 0) + (rates_out ? 24 : 0)) +
+                          2.0 * S * TRACK_STATE * 8,
+                      rows * (1.0 + K) * 3000.0, [&] {
+    return launch_track_step_modes(tr->prm, tr->state, mode_quat, mode_mass, mode_cov, n_modes, K, pos, cov, status, T,
+                                   S, quat_out, pos_out, d2, cov_out, rates_out, track_status, chosen, s);
+  }));
+  return SPEF_OK;
+}
+
 }  // extern "C"

@@ -33,22 +33,7 @@ constexpr int COV_NPOS = 7;    // position workgroup: 6 (g - t^)(g - t^)^T + sum
 __device__ __forceinline__ bool cov_finite(double x) { return fabs(x) < INFINITY; }
 __device__ __forceinline__ bool cov_mass_ok(double sp) { return sp > 0.0 && sp < INFINITY; }
 
-// Sum accumulator k of every thread (sh[k][tid]) into out[k], k < nacc: 16-lane row r of the workgroup takes
-// accumulators r, r + 16, ...; each lane adds 16 interleaved partials, the row adds its lanes by DPP. Ends on a barrier.
-__device__ __forceinline__ void cov_reduce(const double (*sh)[256], double* out, int nacc) {
-  const int tid = threadIdx.x, j = tid & 15;
-  for (int k = tid >> 4; k < nacc; k += 16) {
-    double a = 0.0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a += sh[k][j + 16 * r];
-    a = dpp_add_d<0xB1>(a);    // quad_perm [1,0,3,2]
-    a = dpp_add_d<0x4E>(a);    // quad_perm [2,3,0,1]
-    a = dpp_add_d<0x141>(a);   // row_half_mirror
-    a = dpp_add_d<0x140>(a);   // row_mirror
-    if (j == 0) out[k] = a;
-  }
-  __syncthreads();
-}
+// (the workgroup's fixed-order sum of the accumulators, cov_reduce: spef_reduce.hpp)
 
 // inv(a) of the symmetric 4 x 4 a (packed upper triangle t: 0:00 1:01 2:02 3:03 4:11 5:12 6:13 7:22 8:23 9:33) through
 // its Cholesky factor a = L L^T, inv = L^-T L^-1. -> false when a is not positive definite to fp64: a pivot that is not

@@ -64,6 +64,105 @@ __device__ __forceinline__ void track_rotate(const double (&w)[3], const double 
 
 __device__ __forceinline__ bool track_finite(double x) { return fabs(x) < INFINITY; }
 
+// Step 4 of spe/track.py for one measurement (q_m, t_m) against the prediction (q-, t-, P- in LDS): the innovation y, R
+// from the row's covariance (cov_at(i, j), used when have_cov and all 36 entries are finite; diag(r) otherwise),
+// S = P-[0:6, 0:6] + R = L L^T, z = L^-1 y and d2 = z^T z. -> false on a pivot that is not positive and finite (d2 is
+// then left as it was). inv[j] = 1 / L[j][j]. Uniform on every lane.
+template <class CovAt>
+__device__ __forceinline__ bool track_innovation(const TrackParams& prm, const double* sPm, const double (&qm)[4],
+                                                 const double (&tm)[3], const double (&qp)[4], const double (&tp)[3],
+                                                 bool have_cov, CovAt cov_at, double (&L)[6][6], double (&inv)[6],
+                                                 double (&z)[6], double& d2) {
+  double R[6][6];
+  bool use_cov = have_cov;
+  if (use_cov) {
+    double c[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        c[i][j] = cov_at(i, j);
+        use_cov = use_cov && track_finite(c[i][j]);
+      }
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j <= i; ++j) R[i][j] = prm.cov_scale * ((c[i][j] + c[j][i]) * 0.5);
+  }
+  if (!use_cov) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j <= i; ++j) R[i][j] = i == j ? prm.r[i / 3] : 0.0;
+  }
+  double qu[4] = {qm[0], qm[1], qm[2], qm[3]};
+  track_unit(qu);
+  const double qc[4] = {qp[0], -qp[1], -qp[2], -qp[3]};
+  double d[4];
+  track_qmul(qu, qc, d);
+  if (d[0] < 0.0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = -d[k];
+  }
+  const double n2 = d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
+  const double n = dsqrt(n2);
+  const double fl = n < 1e-8 ? 2.0 / d[0] * (1.0 - n2 / (3.0 * d[0] * d[0])) : 2.0 * atan2(n, d[0]) * rcp_nr(n);
+  const double y[6] = {fl * d[1], fl * d[2], fl * d[3], tm[0] - tp[0], tm[1] - tp[1], tm[2] - tp[2]};
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double dd = sPm[12 * j + j] + R[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) dd -= L[j][k] * L[j][k];
+    const bool good = dd > 0.0 && dd < INFINITY;
+    ok = ok && good;
+    dd = good ? dd : 1.0;
+    inv[j] = rsq_nr(dd);
+    L[j][j] = dd * inv[j];
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double a = sPm[12 * i + j] + R[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) a -= L[i][k] * L[j][k];
+      L[i][j] = a * inv[j];
+    }
+  }
+  if (ok) {
+    d2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      double a = y[i];
+#pragma unroll
+      for (int k = 0; k < i; ++k) a -= L[i][k] * z[k];
+      z[i] = a * inv[i];
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) d2 += z[k] * z[k];
+  }
+  return ok;
+}
+
+// The orientation candidates of spef_track_step_modes (the outputs of spef_decode_modes, K per row).
+struct TrackModes {
+  const float* quat;   // [T*S][K][4]
+  const float* mass;   // [T*S][K]
+  const float* cov3;   // [T*S][K][9]: candidate k's theta block, in place of cov's [0:3, 0:3]
+  const int* n;        // [T*S] candidates in the row
+  int K;
+  int* chosen;         // [T*S] the candidate taken, -1: none
+};
+
+// Candidate k of row `row`: its quaternion and mass as doubles -> whether it is valid (the quaternion finite and
+// non-zero, the mass finite and > 0).
+__device__ __forceinline__ bool track_candidate(const TrackModes& md, size_t row, int k, double (&qk)[4], double& mk) {
+  const float* qf = md.quat + 4 * (row * md.K + k);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) qk[c] = (double)qf[c];
+  mk = (double)md.mass[row * md.K + k];
+  const double n2 = qk[0] * qk[0] + qk[1] * qk[1] + qk[2] * qk[2] + qk[3] * qk[3];
+  return n2 > 0.0 && n2 < INFINITY && mk > 0.0 && mk < INFINITY;
+}
+
 __global__ __launch_bounds__(64) void track_step_kernel(TrackParams prm, double* __restrict__ state, const float* quat,
                                                         const float* pos, const float* __restrict__ cov,
                                                         const int* __restrict__ status, int T, int S, float* quat_out,
@@ -325,6 +424,251 @@ __global__ __launch_bounds__(64) void track_step_kernel(TrackParams prm, double*
   for (int e = lane; e < 144; e += 64) st[16 + e] = sP[e];
 }
 
+// spef_track_step_modes: track_step_kernel with the measurement's orientation chosen among the candidates of md -- the
+// one the prediction makes most likely (the smallest d2_k + 2 sum_j ln L_k[j][j] - 2 ln mass_k, ties to the lowest k)
+// or, without a track, the lowest valid k. Everything around the choice is track_step_kernel's text; step 4 is the
+// device function track_innovation, evaluated per candidate. The two kernels are kept apart because
+// track_step_kernel has to stay the machine code it was (tools/asm_same.py against the commit before this kernel came):
+// sharing one templated body moved where the compiler fuses multiply-adds in it, and its fp64 state by an ulp.
+// tests/test_gpu_modes.py holds the two against each other bit for bit at K = 1.
+__global__ __launch_bounds__(64) void track_step_modes_kernel(TrackParams prm, double* __restrict__ state, TrackModes md,
+                                                              const float* pos, const float* __restrict__ cov,
+                                                              const int* __restrict__ status, int T, int S,
+                                                              float* quat_out, float* pos_out,
+                                                              float* __restrict__ d2_out, float* __restrict__ cov_out,
+                                                              float* __restrict__ rates_out,
+                                                              int* __restrict__ track_status) {
+  __shared__ double sP[144], sPm[144], sW[72], sD[12];
+  const int s = blockIdx.x, lane = threadIdx.x;
+  if (s >= S) return;   // uniform per wave
+  double* st = state + (size_t)s * TRACK_STATE;
+  double have = st[0], coast = st[1];
+  double q[4], t[3], w[3], v[3];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) q[k] = st[3 + k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    t[k] = st[7 + k];
+    w[k] = st[10 + k];
+    v[k] = st[13 + k];
+  }
+  for (int e = lane; e < 144; e += 64) sP[e] = st[16 + e];
+  __syncthreads();
+
+  for (int f = 0; f < T; ++f) {
+    const size_t row = (size_t)f * S + s;
+    // ---- measurement (every lane reads the same words: a broadcast)
+    float qf[4], tf[3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) qf[k] = md.quat[4 * row * md.K + k];   // candidate 0 is what passes through
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tf[k] = pos[3 * row + k];
+    const int dst = status ? status[row] : 0;
+    double qm[4], tm[3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) qm[k] = (double)qf[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tm[k] = (double)tf[k];
+    int pick = -1, nm = 0;   // the candidate taken, the candidates to look at
+    if ((dst & 15) == 0 && track_finite(tm[0]) && track_finite(tm[1]) && track_finite(tm[2]))
+      nm = min(max(md.n[row], 0), md.K);
+    bool valid = nm > 0;   // with a track the candidates are weighed against the prediction below
+    if (have == 0.0) {   // without one the lowest valid candidate (the heaviest mode) starts it
+      for (int k = 0; k < nm; ++k) {
+        double qk[4], mk;
+        if (pick < 0 && track_candidate(md, row, k, qk, mk)) {
+          pick = k;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) qm[c] = qk[c];
+        }
+      }
+      valid = pick >= 0;
+    }
+    int ts = 0;
+    double d2 = NAN;
+    bool start = false;   // start the track (again) from this measurement
+    bool pass = false;    // no track and nothing to start one from: the row goes through as it came
+
+    if (have == 0.0) {
+      if (valid) {
+        start = true;
+        d2 = 0.0;
+      } else {
+        pass = true;
+        ts = TS_INVALID | TS_NO_TRACK;
+      }
+    } else {
+      // ---- predict: P- = F P F^T + Q, F = [[I, I], [0, I]]; lane e owns entries e, e + 64, e + 128
+      for (int e = lane; e < 144; e += 64) {
+        const int i = e / 12, j = e - 12 * i;
+        double p;
+        if (i < 6 && j < 6) {
+          p = ((sP[12 * i + j] + (sP[12 * i + 6 + j] + sP[12 * j + 6 + i])) + sP[12 * (i + 6) + 6 + j]) +
+              (i == j ? prm.q[i / 3] : 0.0);
+        } else if (i < 6) {
+          p = sP[12 * i + j] + sP[12 * (i + 6) + j];
+        } else if (j < 6) {
+          p = sP[12 * j + i] + sP[12 * (j + 6) + i];
+        } else {
+          p = sP[e] + (i == j ? prm.q[i / 3] : 0.0);
+        }
+        sPm[e] = p;
+      }
+      double qp[4], tp[3];
+      track_rotate(w, q, q, qp);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) tp[k] = t[k] + v[k];
+      __syncthreads();
+
+      // ---- innovation, S = P-[0:6, 0:6] + R = L L^T, z = L^-1 y, d2 = z^T z (uniform on every lane)
+      bool ok = false;
+      double L[6][6], inv[6], z[6];
+      if (valid) {
+        double best = INFINITY;
+        for (int k = 0; k < nm; ++k) {
+          double qk[4], mk, Lk[6][6], ik[6], zk[6], dk = NAN;
+          if (!track_candidate(md, row, k, qk, mk)) continue;
+          const float* c3 = md.cov3 + 9 * (row * md.K + k);   // C_k: cov with the theta block of candidate k
+          if (!track_innovation(prm, sPm, qk, tm, qp, tp, true, [&](int i, int j) {
+                return i < 3 && j < 3 ? (double)c3[3 * i + j] : (double)cov[36 * row + 6 * i + j];
+              }, Lk, ik, zk, dk))
+            continue;
+          double lnl = 0.0;   // sum_j ln L[j][j] = ln det(S) / 2
+#pragma unroll
+          for (int j = 0; j < 6; ++j) lnl += log(Lk[j][j]);
+          const double cost = (dk + 2.0 * lnl) - 2.0 * log(mk);
+          if (pick < 0 || cost < best) {
+            pick = k;
+            best = cost;
+            ok = true;
+            d2 = dk;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) qm[c] = qk[c];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+              inv[i] = ik[i];
+              z[i] = zk[i];
+#pragma unroll
+              for (int j = 0; j <= i; ++j) L[i][j] = Lk[i][j];
+            }
+          }
+        }
+      }
+      if (!ok) {
+        ts = TS_INVALID;
+      } else if (prm.gate_chi2 > 0.0 && d2 > prm.gate_chi2) {
+        ts = TS_GATED;
+      }
+
+      if (ts != 0) {
+        if (ts == TS_GATED && coast + 1.0 > prm.max_coast) {
+          start = true;
+          ts = TS_GATED | TS_REINIT;
+        } else {   // coast: the state becomes the prediction, w and v are kept
+          coast += 1.0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) q[k] = qp[k];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) t[k] = tp[k];
+          for (int e = lane; e < 144; e += 64) sP[e] = sPm[e];   // the entries this lane wrote
+        }
+      } else {
+        // ---- update through the factor: W = P-[:, 0:6] L^-T (K = W L^-1, K S K^T = W W^T), delta = W z
+        if (lane < 12) {
+          double wr[6], dl = 0.0;
+#pragma unroll
+          for (int k = 0; k < 6; ++k) {
+            double a = sPm[12 * lane + k];
+#pragma unroll
+            for (int m = 0; m < k; ++m) a -= wr[m] * L[k][m];
+            wr[k] = a * inv[k];
+            sW[6 * lane + k] = wr[k];
+          }
+#pragma unroll
+          for (int k = 0; k < 6; ++k) dl += wr[k] * z[k];
+          sD[lane] = dl;
+        }
+        __syncthreads();
+        for (int e = lane; e < 144; e += 64) {
+          const int i = e / 12, j = e - 12 * i;
+          double p = sPm[e];
+#pragma unroll
+          for (int k = 0; k < 6; ++k) p -= sW[6 * i + k] * sW[6 * j + k];
+          sP[e] = p;
+        }
+        const double dth[3] = {sD[0], sD[1], sD[2]};
+        double qn[4];
+        track_rotate(dth, qp, q, qn);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = qn[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          t[k] = tp[k] + sD[3 + k];
+          w[k] += sD[6 + k];
+          v[k] += sD[9 + k];
+        }
+        coast = 0.0;
+      }
+    }
+
+    if (start) {   // q = q_m / |q_m| (in the previous output's hemisphere when there was one), w = v = 0, P = diag(p0)
+      double qs[4] = {qm[0], qm[1], qm[2], qm[3]};
+      track_unit(qs);
+      const bool flip = have != 0.0 && qs[0] * q[0] + qs[1] * q[1] + qs[2] * q[2] + qs[3] * q[3] < 0.0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) q[k] = flip ? -qs[k] : qs[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        t[k] = tm[k];
+        w[k] = 0.0;
+        v[k] = 0.0;
+      }
+      for (int e = lane; e < 144; e += 64) {
+        const int i = e / 12, j = e - 12 * i;
+        sP[e] = i == j ? prm.p0[i / 3] : 0.0;
+      }
+      have = 1.0;
+      coast = 0.0;
+    }
+    __syncthreads();   // P of this frame is complete
+
+    // ---- outputs
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) quat_out[4 * row + k] = pass ? qf[k] : (float)q[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) pos_out[3 * row + k] = pass ? tf[k] : (float)t[k];
+      if (d2_out) d2_out[row] = (float)d2;
+      track_status[row] = ts;
+      md.chosen[row] = pick;
+    }
+    if (rates_out && lane < 6) {
+      const double rv = lane == 0 ? w[0] : lane == 1 ? w[1] : lane == 2 ? w[2] : lane == 3 ? v[0] : lane == 4 ? v[1] : v[2];
+      rates_out[6 * row + lane] = pass ? NAN : (float)rv;
+    }
+    if (cov_out && lane < 36) {
+      const int i = lane / 6, j = lane - 6 * i;
+      cov_out[36 * row + lane] = pass ? NAN : (float)sP[12 * i + j];
+    }
+  }
+
+  // ---- the state goes back as fp64: the next call continues bit for bit
+  if (lane == 0) {
+    st[0] = have;
+    st[1] = coast;
+    st[2] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) st[3 + k] = q[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      st[7 + k] = t[k];
+      st[10 + k] = w[k];
+      st[13 + k] = v[k];
+    }
+  }
+  for (int e = lane; e < 144; e += 64) st[16 + e] = sP[e];
+}
+
 __global__ __launch_bounds__(256) void track_reset_kernel(double* __restrict__ state, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) state[i] = 0.0;
 }
@@ -341,6 +685,17 @@ hipError_t launch_track_step(const TrackParams& p, double* state, const float* q
                              float* d2, float* cov_out, float* rates_out, int* track_status, hipStream_t s) {
   track_step_kernel<<<S, 64, 0, s>>>(p, state, quat, pos, cov, status, T, S, quat_out, pos_out, d2, cov_out, rates_out,
                                      track_status);
+  return hipGetLastError();
+}
+
+hipError_t launch_track_step_modes(const TrackParams& p, double* state, const float* mode_quat, const float* mode_mass,
+                                   const float* mode_cov, const int* n_modes, int K, const float* pos, const float* cov,
+                                   const int* status, int T, int S, float* quat_out, float* pos_out, float* d2,
+                                   float* cov_out, float* rates_out, int* track_status, int* chosen, hipStream_t s) {
+  if (K < 1 || K > MODES_MAX) return hipErrorInvalidValue;
+  const TrackModes md{mode_quat, mode_mass, mode_cov, n_modes, K, chosen};
+  track_step_modes_kernel<<<S, 64, 0, s>>>(p, state, md, pos, cov, status, T, S, quat_out, pos_out, d2, cov_out,
+                                           rates_out, track_status);
   return hipGetLastError();
 }
 

@@ -210,6 +210,18 @@ hipError_t launch_decode_cov(int ori_cls, int pos_cls, const float* ori_pdf, int
                              const float* pos_pdf, int n_pos, const double* grid, const float* quat, const float* pos,
                              int B, const CovParams& prm, float* cov, float* ori_hinv, int* cov_status, hipStream_t s);
 
+// ---- multi-hypothesis orientation decode (k_modes.hip; the algorithm is stated in spef_amd/spe/modes.py) ----
+constexpr int MODES_MAX = 4;   // SPEF_MODES_MAX
+struct ModesParams {
+  int k_max, rounds;
+  double cos_half_sep, seed_rel, min_mass, floor_var;   // cos_half_sep = cos(sep / 2)
+};
+// Up to k_max modes of every row of ori_pdf [B][n_ori]: mode_quat [B][k_max][4], mode_mass [B][k_max], mode_cov
+// [B][k_max][9] (NaN past n_modes[b]), n_modes [B], modes_status [B] (1 = the row is not a PDF). One workgroup per row.
+hipError_t launch_decode_modes(const float* ori_pdf, int n_ori, const double* q_bins, int B, const ModesParams& prm,
+                               float* mode_quat, float* mode_mass, float* mode_cov, int* n_modes, int* modes_status,
+                               hipStream_t s);
+
 // ---- adaptive video filter (k_video.hip; TemporalPDF.update_pdf, src/temporal/pdf_compare.py:94-134) ----
 // Frames are time-major: row t * S + s is time step t of stream s. One head (ori or pos) of the filter:
 struct VideoHead {
@@ -277,6 +289,14 @@ struct TrackParams {
 hipError_t launch_track_step(const TrackParams& p, double* state, const float* quat, const float* pos,
                              const float* cov, const int* status, int T, int S, float* quat_out, float* pos_out,
                              float* d2, float* cov_out, float* rates_out, int* track_status, hipStream_t s);
+// The same step with up to K (1..MODES_MAX) orientation candidates per row: mode_quat [T*S][K][4], mode_mass [T*S][K],
+// mode_cov [T*S][K][9] (the theta block of candidate k; cov [T*S][36] supplies the rest), n_modes [T*S]; the kernel
+// picks the candidate of largest likelihood under the prediction (the heaviest valid one without a track) and writes
+// its index to chosen [T*S] (-1: none). status, d2, cov_out and rates_out may be null.
+hipError_t launch_track_step_modes(const TrackParams& p, double* state, const float* mode_quat, const float* mode_mass,
+                                   const float* mode_cov, const int* n_modes, int K, const float* pos, const float* cov,
+                                   const int* status, int T, int S, float* quat_out, float* pos_out, float* d2,
+                                   float* cov_out, float* rates_out, int* track_status, int* chosen, hipStream_t s);
 // Zero n doubles at state (a stream without a track); copy n doubles (get / set state).
 hipError_t launch_track_reset(double* state, int64_t n, hipStream_t s);
 hipError_t launch_track_copy(double* dst, const double* src, int64_t n, hipStream_t s);

@@ -63,4 +63,22 @@ __device__ __forceinline__ double block_sum256_d(double v, double* sh) {
   return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
+// Sum accumulator k of every thread of a 256-thread workgroup (sh[k][tid]) into out[k], k < nacc: 16-lane row r of the
+// workgroup takes accumulators r, r + 16, ...; each lane adds 16 interleaved partials, the row adds its lanes by DPP.
+// Ends on a barrier. (The decode covariance, k_cov.hip, and the multi-hypothesis decode, k_modes.hip.)
+__device__ __forceinline__ void cov_reduce(const double (*sh)[256], double* out, int nacc) {
+  const int tid = threadIdx.x, j = tid & 15;
+  for (int k = tid >> 4; k < nacc; k += 16) {
+    double a = 0.0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a += sh[k][j + 16 * r];
+    a = dpp_add_d<0xB1>(a);    // quad_perm [1,0,3,2]
+    a = dpp_add_d<0x4E>(a);    // quad_perm [2,3,0,1]
+    a = dpp_add_d<0x141>(a);   // row_half_mirror
+    a = dpp_add_d<0x140>(a);   // row_mirror
+    if (j == 0) out[k] = a;
+  }
+  __syncthreads();
+}
+
 }  // namespace spef

@@ -43,6 +43,7 @@ SIGNATURES = {
     'spef_set_decode_tables': (_i, [_vp, _vp, _i, _vp, _i]),
     'spef_decode': (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'spef_decode_cov': (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    'spef_decode_modes': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'spef_video_create': (_i, [_vp, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(_vp)]),
     'spef_video_reset': (_i, [_vp, _i, _vp]),
     'spef_video_set_state': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -59,6 +60,8 @@ SIGNATURES = {
     'spef_track_get_state': (_i, [_vp, _i, _i, _vp, _vp]),
     'spef_track_set_state': (_i, [_vp, _i, _i, _vp, _vp]),
     'spef_track_step': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'spef_track_step_modes': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp]),
     'spef_track_destroy': (_i, [_vp]),
     'spef_observer_create': (_i, [_vp, C.POINTER(_vp)]),
     'spef_observer_info': (_i, [_vp, _ip, _ip]),
@@ -100,6 +103,14 @@ class CovParams(C.Structure):     # spef_cov_params
 
 
 COV_ORI, COV_HINV, COV_POS = 1, 2, 4   # spef_decode_cov's cov_status bits
+
+
+class ModesParams(C.Structure):   # spef_modes_params
+    _fields_ = [('k_max', C.c_int), ('rounds', C.c_int), ('sep_deg', C.c_double), ('seed_rel', C.c_double),
+                ('min_mass', C.c_double), ('floor_var', C.c_double)]
+
+
+MODES_MAX = 4                          # SPEF_MODES_MAX
 
 
 class SpefError(RuntimeError):

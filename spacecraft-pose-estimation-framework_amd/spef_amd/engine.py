@@ -261,6 +261,44 @@ class PoseTracker:
             out['rates'] = ro
         return out
 
+    def step_modes(self, dec: dict, T: int, want_cov: bool = False, want_rates: bool = False) -> dict:
+        """``step`` with several orientation candidates per row: ``dec`` holds ``Engine.decode_modes``' 'mode_quat'
+        [B x K x 4], 'mode_mass' [B x K], 'mode_cov' [B x K x 3 x 3] and 'n_modes' [B] next to 'pos', 'cov' (required:
+        ``decode_cov``'s, which supplies the t block) and, when present, 'status'. The tracker takes, per row, the
+        candidate its prediction makes most likely (the heaviest valid one while the stream has no track; the rule is
+        stated in ``spe.track.PoseTrackerHost.step_modes``) and then steps as ``step`` does. -> ``step``'s dict and
+        'chosen' [B] int32 (the candidate taken, -1: none). One kernel on the current stream."""
+        mq, mm, mc, nm = dec['mode_quat'], dec['mode_mass'], dec['mode_cov'], dec['n_modes']
+        pos, status, cov = dec['pos'], dec.get('status'), dec.get('cov')
+        B, S, dev = mq.shape[0], self.n_streams, self.device
+        K = mq.shape[1]
+        assert T >= 1 and B == T * S, f'{B} rows are not T = {T} steps of {S} streams'
+        assert cov is not None, 'step_modes needs the pose covariance (decode_cov)'
+        assert 1 <= K <= L.MODES_MAX and mq.shape == (B, K, 4) and mm.shape == (B, K) and mc.numel() == B * K * 9
+        assert pos.shape == (B, 3) and cov.numel() == B * 36 and nm.numel() == B
+        for t in (mq, mm, mc, pos, cov):
+            assert t.device == dev and t.is_contiguous() and t.dtype == torch.float32
+        assert nm.device == dev and nm.dtype == torch.int32 and nm.is_contiguous()
+        if status is not None:
+            assert status.device == dev and status.dtype == torch.int32 and status.numel() == B
+            status = status.contiguous()
+        qo = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        po = torch.empty((B, 3), dtype=torch.float32, device=dev)
+        d2 = torch.empty((B,), dtype=torch.float32, device=dev)
+        ts = torch.empty((B,), dtype=torch.int32, device=dev)
+        ch = torch.empty((B,), dtype=torch.int32, device=dev)
+        co = torch.empty((B, 6, 6), dtype=torch.float32, device=dev) if want_cov else None
+        ro = torch.empty((B, 6), dtype=torch.float32, device=dev) if want_rates else None
+        L.check(self.lib.spef_track_step_modes(self.handle, _ptr(mq), _ptr(mm), _ptr(mc), _ptr(nm), K, _ptr(pos),
+                                               _ptr(cov), _ptr(status), T, S, _ptr(qo), _ptr(po), _ptr(d2), _ptr(co),
+                                               _ptr(ro), _ptr(ts), _ptr(ch), _stream(dev)))
+        out = {'ori': qo, 'pos': po, 'mahalanobis': d2, 'track_status': ts, 'chosen': ch}
+        if want_cov:
+            out['cov'] = co
+        if want_rates:
+            out['rates'] = ro
+        return out
+
     def reset(self, stream: Optional[int] = None) -> None:
         """Forget one stream's track (all streams: None); enqueued on the current stream."""
         L.check(self.lib.spef_track_reset(self.handle, -1 if stream is None else int(stream), _stream(self.device)))
@@ -543,6 +581,39 @@ class Engine:
         if want_hinv:
             dec['ori_hinv'] = hinv
         return dec
+
+    def decode_modes(self, dec_or_pdf, k_max: int = 2, sep_deg: float = 45.0, seed_rel: float = 0.1,
+                     min_mass: float = 0.05, rounds: int = 3, floor_var: float = 0.0) -> dict:
+        """The multi-hypothesis orientation decode (csrc/k_modes.hip; ``spe.modes`` is its NumPy twin and states the
+        algorithm): up to ``k_max`` orientations that a soft-classification PDF holds at once, where ``decode`` returns
+        their one Markley average. ``dec_or_pdf``: an orientation PDF [B x n_ori] (float32, on the device) or a dict
+        holding one as 'ori_soft' (what ``decode`` or ``VideoFilter.step`` returned), which then also receives the
+        results. -> {'mode_quat' [B x k_max x 4] (unit, scalar part >= 0, by descending mass), 'mode_mass'
+        [B x k_max], 'mode_cov' [B x k_max x 3 x 3] (each mode's theta block; ``floor_var`` is added to its diagonal),
+        all NaN past 'n_modes' [B], and 'modes_status' [B] (1: the row is not a PDF; a word of its own)}. With one mode
+        the result is the plain decode, mass 1 and ``decode_cov``'s theta block. ``PoseTracker.step_modes`` takes the
+        dict. One launch on the current stream; no host sync."""
+        from .spe import modes as MD
+        k_max, rounds, sep_deg, seed_rel, min_mass, floor_var = MD.check_params(k_max, sep_deg, seed_rel, min_mass,
+                                                                                rounds, floor_var)
+        dec = dec_or_pdf if isinstance(dec_or_pdf, dict) else None
+        pdf = dec.get('ori_soft') if dec is not None else dec_or_pdf
+        assert pdf is not None, 'decode_modes needs the orientation PDF (want_soft; a classification head)'
+        dev = self.device
+        assert pdf.dim() == 2 and pdf.device == dev and pdf.is_contiguous() and pdf.dtype == torch.float32
+        B = pdf.shape[0]
+        prm = L.ModesParams(k_max, rounds, sep_deg, seed_rel, min_mass, floor_var)
+        mq = torch.empty((B, k_max, 4), dtype=torch.float32, device=dev)
+        mm = torch.empty((B, k_max), dtype=torch.float32, device=dev)
+        mc = torch.empty((B, k_max, 3, 3), dtype=torch.float32, device=dev)
+        nm = torch.empty((B,), dtype=torch.int32, device=dev)
+        ms = torch.empty((B,), dtype=torch.int32, device=dev)
+        L.check(self.lib.spef_decode_modes(self.ctx, _ptr(pdf), pdf.shape[1], B, C.byref(prm), _ptr(mq), _ptr(mm),
+                                           _ptr(mc), _ptr(nm), _ptr(ms), _stream(dev)))
+        out = {'mode_quat': mq, 'mode_mass': mm, 'mode_cov': mc, 'n_modes': nm, 'modes_status': ms}
+        if dec is not None:
+            dec.update(out)
+        return out
 
     def video_filter(self, n_streams: int, metric: str = 'l2', n_ori: float = 0.8, alpha_ori: float = 16.49,
                      n_pos: float = 0.5, alpha_pos: float = 48.64) -> 'VideoFilter':

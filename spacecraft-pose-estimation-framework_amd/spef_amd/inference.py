@@ -20,6 +20,8 @@ pose of any head, keypoint mode included, with the device tracker (csrc/k_track.
 ``pose_video`` = {'ori', 'pos', 'mahalanobis', 'track_status', 'keypoints', 'bbox'}. Its parameters are
 ``Inference.tracker_params``; its state lives on the device and ``reset()`` clears it. ``Inference.tracker_pdf_cov``
 (off by default) makes the measurement covariance that of the soft-classification PDFs (``Engine.decode_cov``).
+``Inference.tracker_modes = K`` (0 by default) keeps up to K orientations of an ambiguous orientation PDF per frame
+(``Engine.decode_modes``) and lets the tracker pick among them; the still pose then carries 'modes'.
 """
 from __future__ import annotations
 
@@ -63,6 +65,7 @@ class Inference:
         self.pdf_adapt_pos = TemporalPDF(n=0.5, alpha=48.64, distance_metric='l2')
         self.tracker_params = {}     # video_type 'Tracker': the parameters of Engine.tracker (q, p0, r, gate_chi2, ...)
         self.tracker_pdf_cov = False  # video_type 'Tracker': SPEMi355x.predict_tracked(pdf_cov=True), the PDFs' covariance
+        self.tracker_modes = 0       # video_type 'Tracker': predict_tracked(modes=K), up to K orientation hypotheses per frame
         self.img_size = None
         self.device = device
         self.dtype = dtype
@@ -154,12 +157,16 @@ class Inference:
             raise ValueError("video filtering 'Tracker' needs the 'gpu_mi355x' engine")
         T = int(images.shape[0])
         pdf_cov = {'pdf_cov': True} if self.tracker_pdf_cov else {}
-        still, tracked, latency_ms = eng.predict_tracked(images, 1, **pdf_cov, **self.tracker_params)
+        modes = {'modes': int(self.tracker_modes)} if self.tracker_modes else {}
+        still, tracked, latency_ms = eng.predict_tracked(images, 1, **pdf_cov, **modes, **self.tracker_params)
         still = dict(still)
         still['ori'] = self._still_pole(still['ori'])
+        found = still.pop('modes', None)     # tracker_modes: a dict of per-frame arrays
         out = []
         for t in range(T):
             pose_still = {k: v[t] for k, v in still.items()}
+            if found is not None:
+                pose_still['modes'] = {k: v[t] for k, v in found.items()}
             self._visual(pose_still)
             pose_video = {k: v[t] for k, v in tracked.items()}
             if su.keypoints is not None:

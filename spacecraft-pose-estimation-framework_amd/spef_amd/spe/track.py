@@ -34,6 +34,10 @@ started again from this row; 8 = no track, row passed through.
 
 Rows are time-major (row ``t * S + s`` = step t of stream s) as on the video and scoring paths, and a stream's result
 depends neither on S nor on how a sequence is cut into calls.
+
+``step_modes`` (``spef_track_step_modes``) is the same filter fed up to K orientation candidates per row, the modes of
+``spe.modes``: the candidate the prediction makes most likely becomes (q_m, cov) of step 4 -- its docstring states the
+rule -- and steps 2 to 7 run unchanged on it. This is what resolves a two-peaked orientation PDF.
 """
 from __future__ import annotations
 
@@ -144,6 +148,81 @@ class PoseTrackerHost:
         st[7:10] = tm
         st[16:] = np.diag(np.repeat(self.p0, 3)).reshape(-1)
 
+    def _predict(self, st):
+        """Step 3 -> (P-, q-, t-)."""
+        q, t, w, v = st[3:7].copy(), st[7:10].copy(), st[10:13].copy(), st[13:16].copy()
+        P = st[16:].reshape(12, 12)
+        A, B, C = P[:6, :6], P[:6, 6:], P[6:, 6:]
+        Qd = np.diag(np.repeat(self.q, 3))
+        Pm = np.empty((12, 12))
+        Pm[:6, :6] = ((A + (B + B.T)) + C) + Qd[:6, :6]
+        Pm[:6, 6:] = B + C
+        Pm[6:, :6] = Pm[:6, 6:].T
+        Pm[6:, 6:] = C + Qd[6:, 6:]
+        return Pm, _unit(qmul(qexp(w), q)), t + v
+
+    def _innovation(self, Pm, qp, tp, qm, tm, cov):
+        """Step 4 -> (L, ok, z, d2): z is None and d2 NaN when a pivot of S fails."""
+        qn = _unit(qm)
+        y = np.concatenate([qlog(qmul(qn, qp * [1.0, -1.0, -1.0, -1.0])), tm - tp])
+        R = np.diag(np.repeat(self.r, 3))
+        if cov is not None and np.all(np.isfinite(cov)):
+            cov = np.asarray(cov, np.float64).reshape(6, 6)
+            R = self.cov_scale * ((cov + cov.T) * 0.5)
+        L, ok = _chol6(Pm[:6, :6] + R)
+        z, d2 = None, np.nan
+        if ok:
+            z = np.zeros(6)
+            for i in range(6):
+                s = y[i]
+                for k in range(i):
+                    s -= L[i, k] * z[k]
+                z[i] = s / L[i, i]
+            d2 = 0.0
+            for k in range(6):
+                d2 += z[k] * z[k]
+        return L, ok, z, d2
+
+    def _frame_modes(self, st, cands, tm, cov, status):
+        """One frame of one stream with orientation candidates ``cands`` = [(q_k, mass_k, theta block_k)] and the
+        shared (t_m, cov, status) -> (quat, pos, d2, track status, chosen, cost gap). The choice is made here; steps
+        2 to 7 are ``_frame``'s, on the chosen (q_k, C_k)."""
+        base = (int(status) & 15) == 0 and bool(np.all(np.isfinite(tm)))
+        Cs, ok_k = [], []
+        for qk, mk, blk in cands:
+            C = np.array(cov, np.float64).reshape(6, 6)
+            C[:3, :3] = np.asarray(blk, np.float64).reshape(3, 3)
+            Cs.append(C)
+            n2 = float(qk @ qk)
+            ok_k.append(base and bool(np.all(np.isfinite(qk))) and 0.0 < n2 < np.inf and bool(np.isfinite(mk)) and
+                        mk > 0.0)
+        pick, gap = -1, np.inf
+        if st[0] == 0.0:
+            pick = next((k for k, g in enumerate(ok_k) if g), -1)
+        else:
+            Pm, qp, tp = self._predict(st)
+            costs = {}
+            for k, (qk, mk, _) in enumerate(cands):
+                if not ok_k[k]:
+                    continue
+                L, ok, _, d2 = self._innovation(Pm, qp, tp, qk, tm, Cs[k])
+                if ok:
+                    lnl = 0.0
+                    for j in range(6):
+                        lnl += np.log(L[j, j])
+                    costs[k] = (d2 + 2.0 * lnl) - 2.0 * np.log(mk)
+            for k, c in costs.items():                      # the smallest cost, ties to the lowest k
+                if pick < 0 or c < costs[pick]:
+                    pick = k
+            if len(costs) > 1:
+                rest = sorted(c for k, c in costs.items() if k != pick)
+                gap = rest[0] - costs[pick]
+        if pick < 0:
+            q0 = cands[0][0] if cands else np.full(4, np.nan)
+            qo, to, d2, ts = self._frame(st, np.full(4, np.nan), tm, None, status)
+            return (q0 if ts & NO_TRACK else qo), to, d2, ts, -1, gap
+        return self._frame(st, cands[pick][0], tm, Cs[pick], status) + (pick, gap)
+
     def _frame(self, st, qm, tm, cov, status):
         """One frame of one stream on the state row ``st`` (in place) -> (quat, pos, d2, track status)."""
         valid = (int(status) & 15) == 0 and bool(np.all(np.isfinite(qm))) and bool(np.all(np.isfinite(tm)))
@@ -154,35 +233,10 @@ class PoseTrackerHost:
             self._start(st, qm, tm)
             return st[3:7].copy(), st[7:10].copy(), 0.0, 0
         q, t, w, v = st[3:7].copy(), st[7:10].copy(), st[10:13].copy(), st[13:16].copy()
-        P = st[16:].reshape(12, 12)
-        A, B, C = P[:6, :6], P[:6, 6:], P[6:, 6:]
-        Qd = np.diag(np.repeat(self.q, 3))
-        Pm = np.empty((12, 12))
-        Pm[:6, :6] = ((A + (B + B.T)) + C) + Qd[:6, :6]
-        Pm[:6, 6:] = B + C
-        Pm[6:, :6] = Pm[:6, 6:].T
-        Pm[6:, 6:] = C + Qd[6:, 6:]
-        qp = _unit(qmul(qexp(w), q))
-        tp = t + v
+        Pm, qp, tp = self._predict(st)
         d2, ok = np.nan, False
         if valid:
-            qn = _unit(qm)
-            y = np.concatenate([qlog(qmul(qn, qp * [1.0, -1.0, -1.0, -1.0])), tm - tp])
-            R = np.diag(np.repeat(self.r, 3))
-            if cov is not None and np.all(np.isfinite(cov)):
-                cov = np.asarray(cov, np.float64).reshape(6, 6)
-                R = self.cov_scale * ((cov + cov.T) * 0.5)
-            L, ok = _chol6(Pm[:6, :6] + R)
-            if ok:
-                z = np.zeros(6)
-                for i in range(6):
-                    s = y[i]
-                    for k in range(i):
-                        s -= L[i, k] * z[k]
-                    z[i] = s / L[i, i]
-                d2 = 0.0
-                for k in range(6):
-                    d2 += z[k] * z[k]
+            L, ok, z, d2 = self._innovation(Pm, qp, tp, qm, tm, cov)
         ts = 0
         if not ok:
             ts = INVALID
@@ -244,6 +298,49 @@ class PoseTrackerHost:
                 r = t * S + s
                 qo, to, d2, ts = self._frame(st, quat[r], pos[r], None if cov is None else cov[r], status[r])
                 out['ori'][r], out['pos'][r], out['mahalanobis'][r], out['track_status'][r] = qo, to, d2, ts
+                if ts & NO_TRACK:
+                    out['cov'][r], out['rates'][r] = np.nan, np.nan
+                else:
+                    out['cov'][r] = st[16:].reshape(12, 12)[:6, :6]
+                    out['rates'][r] = st[10:16]
+        return out
+
+    def step_modes(self, mode_quat, mode_mass, mode_cov, n_modes, pos, cov, status=None, T=None) -> dict:
+        """``step`` with up to K orientation candidates per row (``spe.modes.decode_modes_host``'s outputs):
+        ``mode_quat`` [T * S x K x 4], ``mode_mass`` [T * S x K], ``mode_cov`` [T * S x K x 3 x 3], ``n_modes``
+        [T * S]; ``pos`` [T * S x 3] and ``cov`` [T * S x 6 x 6] (required: it supplies the t block) are shared by a
+        row's candidates. Candidate k < n_modes is valid when its quaternion is finite and non-zero and its mass finite
+        and > 0; its covariance C_k is ``cov`` with the theta block replaced by ``mode_cov[k]`` and then goes through
+        step 4's rule. With a track the candidate of smallest cost_k = d2_k + 2 sum_j ln L_k[j][j] - 2 ln mass_k
+        (twice the negative log-likelihood; a failed pivot makes it invalid; ties to the lowest k) is the measurement,
+        without one the lowest valid k; with no valid candidate the measurement is invalid. Steps 2 to 7 then run
+        unchanged. -> ``step``'s dict and 'chosen' [T * S] (-1: none) and 'cost_gap' [T * S] (second-best minus best
+        cost; inf with fewer than two candidates weighed)."""
+        mode_quat = np.asarray(mode_quat, np.float64)
+        B, S = mode_quat.shape[0], self.n_streams
+        K = mode_quat.shape[1]
+        mode_mass = np.asarray(mode_mass, np.float64).reshape(B, K)
+        mode_cov = np.asarray(mode_cov, np.float64).reshape(B, K, 3, 3)
+        n_modes = np.asarray(n_modes).reshape(B)
+        pos = np.asarray(pos, np.float64).reshape(B, 3)
+        cov = np.asarray(cov, np.float64).reshape(B, 6, 6)
+        T = B // S if T is None else int(T)
+        assert T >= 1 and B == T * S and mode_quat.shape == (B, K, 4), f'{B} rows are not T = {T} steps of {S} streams'
+        status = np.zeros(B, np.int64) if status is None else np.asarray(status).reshape(B)
+        out = {'ori': np.empty((B, 4)), 'pos': np.empty((B, 3)), 'mahalanobis': np.empty(B),
+               'track_status': np.zeros(B, np.int32), 'cov': np.empty((B, 6, 6)), 'rates': np.empty((B, 6)),
+               'chosen': np.zeros(B, np.int32), 'cost_gap': np.empty(B)}
+        for s in range(S):
+            st = self._state[s]
+            for t in range(T):
+                r = t * S + s
+                n = int(min(max(n_modes[r], 0), K))
+                cands = [(mode_quat[r, k], mode_mass[r, k], mode_cov[r, k]) for k in range(n)]
+                qo, to, d2, ts, pick, gap = self._frame_modes(st, cands, pos[r], cov[r], status[r])
+                if ts & NO_TRACK:
+                    qo = mode_quat[r, 0]
+                out['ori'][r], out['pos'][r], out['mahalanobis'][r], out['track_status'][r] = qo, to, d2, ts
+                out['chosen'][r], out['cost_gap'][r] = pick, gap
                 if ts & NO_TRACK:
                     out['cov'][r], out['rates'][r] = np.nan, np.nan
                 else:

@@ -254,7 +254,8 @@ class SPEMi355x:
         self._track = None
 
     def predict_tracked(self, images: torch.Tensor, n_streams: int = 1, targets=None, scorer=None,
-                        pdf_cov: bool = False, floor_var=(0.0, 0.0), **params) -> Tuple[Dict, Dict, float]:
+                        pdf_cov: bool = False, floor_var=(0.0, 0.0), modes: int = 0, modes_params=None,
+                        **params) -> Tuple[Dict, Dict, float]:
         """Time-major video frames ``images`` [T * n_streams, ...] (row t * n_streams + s = step t of stream s) ->
         (still pose, tracked pose, latency ms) for every head mode: one batched forward, one decode and one tracker
         step (``Engine.tracker``: an error-state Kalman filter with gating and coasting), all on the GPU. The still
@@ -267,6 +268,11 @@ class SPEMi355x:
         (``Engine.decode_cov`` with ``fixed_var`` = the tracker's ``r`` for a regression head and ``floor_var`` added to
         a classification head's diagonal; a row whose PDF gives no covariance falls back to ``r``), which lets a
         Mahalanobis gate fire; otherwise (the default) the fixed ``r`` is.
+        ``modes=K`` (1..4; 0, the default, is the path above, untouched) keeps up to K orientations of an ambiguous
+        orientation PDF and lets the tracker pick: decode -> ``decode_cov`` -> ``Engine.decode_modes`` (``modes_params``:
+        sep_deg, seed_rel, min_mass, rounds) -> ``PoseTracker.step_modes``. The still pose then has 'modes' = {'quat'
+        [B x K x 4], 'mass' [B x K], 'n' [B], 'chosen' [B]} and the tracked pose 'chosen'. It needs a classification
+        orientation head (AssertionError otherwise).
         The tracker's state persists between calls (``tracker(...).reset()`` starts new videos). ``params``: as
         ``Engine.tracker``. With ``targets`` and ``scorer`` (``engine.scorer(n_streams, 2, capacity)``) track 0 logs the
         still poses and track 1 the tracked ones; a tracked row counts as failed only where it passed through."""
@@ -276,12 +282,22 @@ class SPEMi355x:
         B = x.shape[0]
         if n_streams < 1 or B % n_streams:
             raise AssertionError(f'{B} frames are not whole time steps of {n_streams} streams')
+        modes = int(modes)
+        if modes and (self.keypoint_mode or self.ori_mode != L.CLASSIFICATION):
+            raise AssertionError('modes needs a classification orientation head (a soft PDF)')
+        if modes < 0 or modes > L.MODES_MAX:
+            raise AssertionError(f'modes must be in 0..{L.MODES_MAX}')
         trk = self.tracker(n_streams, **params)
         torch.cuda.synchronize(self.device)
         start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
         raw0, raw1 = self.engine.forward(x)
-        if self.keypoint_mode:
+        if modes:
+            dec = self.engine.decode(self.ori_mode, self.pos_mode, raw0, raw1, want_cov=True, fixed_var=trk.params['r'],
+                                     floor_var=floor_var)
+            self.engine.decode_modes(dec, k_max=modes, floor_var=float(np.asarray(floor_var).reshape(-1)[0]),
+                                     **(modes_params or {}))
+        elif self.keypoint_mode:
             dec = self.engine.decode_keypoints(raw0, apply_sigmoid=True, want_cov=self.keypoint_refine is not None or
                                                self.keypoint_consensus is not None)
         elif pdf_cov:
@@ -289,7 +305,7 @@ class SPEMi355x:
                                      floor_var=floor_var)
         else:
             dec = self.engine.decode(self.ori_mode, self.pos_mode, raw0, raw1)
-        out = trk.step(dec, B // n_streams)
+        out = trk.step_modes(dec, B // n_streams) if modes else trk.step(dec, B // n_streams)
         if targets is not None and scorer is not None:
             if scorer.n_groups != n_streams or scorer.n_tracks < 2:
                 raise AssertionError(f'the scorer needs {n_streams} groups and 2 tracks')
@@ -299,7 +315,12 @@ class SPEMi355x:
         end.record()
         end.synchronize()
         tracked = {k: out[k].cpu().numpy() for k in ('ori', 'pos', 'mahalanobis', 'track_status')}
-        return self._pose(dec, check=False), tracked, start.elapsed_time(end)
+        still = self._pose(dec, check=False)
+        if modes:
+            tracked['chosen'] = out['chosen'].cpu().numpy()
+            still['modes'] = {'quat': dec['mode_quat'].cpu().numpy(), 'mass': dec['mode_mass'].cpu().numpy(),
+                              'n': dec['n_modes'].cpu().numpy(), 'chosen': tracked['chosen']}
+        return still, tracked, start.elapsed_time(end)
 
     def _pose(self, dec, check: bool = True, want_cov: bool = False) -> Dict:
         status = dec['status'].cpu().numpy() if check else np.zeros(1, np.int32)
