@@ -357,6 +357,58 @@ int spef_track_step_modes(spef_track* track, const float* mode_quat, const float
                           int* track_status, int* chosen, void* stream_hip);
 int spef_track_destroy(spef_track* track);
 
+/* Fixed-interval smoothing of a recorded video (opt-in): a Rauch-Tung-Striebel backward pass over the tracker's
+ * posteriors, so that frame k is estimated from every frame of the window and not only from frames 0..k (DESIGN.md
+ * section 3, Smoothing path; spef_amd/spe/smooth.py is the NumPy twin and states every step and the order of every
+ * sum). It is the RTS recursion under the filter's own model, F = [[I6, I6], [0, I6]] (small rotations between
+ * frames), on the error state (theta, t, w, v); it reads no measurement. All arithmetic is fp64.
+ *
+ * spef_track_history: a device buffer of capacity frames x n_streams rows x SPEF_TRACK_STATE_DOUBLES doubles, time-major
+ *   (frame f, stream s at row f * n_streams + s), and the backward pass's workspace. A row is the tracker's state after
+ *   that frame as spef_track_get_state lays it out, with the frame's track_status in slot 2. The number of frames
+ *   recorded is kept by the host in the handle: every call below is checked and sized by it, so a stream capture
+ *   records the frame positions of the calls it holds.
+ * spef_track_history_create: capacity >= 1 and capacity * n_streams * 36 <= 2^31 - 1 (the rows one spef_track_smooth
+ *   call may cover; SPEF_ERR_ARG otherwise); it copies the tracker's parameters, and belongs to that tracker. The only
+ *   call here that allocates or synchronises. spef_track_history_reset: forget every frame (nothing is enqueued).
+ *   spef_track_history_count: write the number of frames recorded to a device int (enqueued).
+ * spef_track_step_hist: spef_track_step, bit for bit in its outputs and in the tracker's state, that also appends the T
+ *   frames to the history. SPEF_ERR_ARG, with nothing enqueued, for what spef_track_step refuses, a history of another
+ *   tracker, or more frames than the capacity has left.
+ * spef_track_history_push: append the tracker's current state as one more frame, with track_status [n_streams] (device)
+ *   as its status words -- how a caller records after spef_track_step_modes or after live T = 1 steps. SPEF_ERR_ARG for
+ *   a NULL pointer, a history of another tracker or a full history.
+ * spef_track_smooth: smooth the frames first .. first + T - 1 (first >= 0, T >= 1, first + T <= the frames recorded;
+ *   SPEF_ERR_ARG otherwise or for a NULL required pointer, with nothing enqueued), every stream on its own.
+ *   quat_io [T*S x 4] / pos_io [T*S x 3]  the filter's outputs for these rows, overwritten by the smoothed pose; the
+ *     quaternion is unit and keeps the hemisphere of the filter's output for the row. cov_out (or NULL) [T*S x 36] the
+ *     pose block of P^s, symmetric bit for bit; rates_out (or NULL) [T*S x 6] the smoothed (w, v). Without cov_out no
+ *     covariance is smoothed at all; the pose does not depend on it, bit for bit.
+ *   smooth_status [T*S]: 0 = smoothed; 1 = the row has no track: quat_io / pos_io are left untouched, cov_out and
+ *     rates_out are NaN; 2 = a chain ends at this row, which is the filter's (x^s = x, P^s = P): the window's last
+ *     frame, a row whose successor has no track or carries track_status & 4 (nothing is smoothed across a
+ *     re-initialisation), and, with 4 as well, a row whose P- of the next frame has a Cholesky pivot that is not
+ *     positive and finite.
+ *   With G = P F^T (P-)^-1 (through the Cholesky factor of P-; (P-, q-, t-) are the filter's prediction from row k):
+ *     delta = G [Log(q^s_{k+1} (x) conj(q-)), t^s_{k+1} - t-, w^s_{k+1} - w_k, v^s_{k+1} - v_k], q^s_k =
+ *     normalise(exp(delta_theta) (x) q_k), (t, w, v)^s_k = (t, w, v)_k + delta, P^s_k = P_k + G (P^s_{k+1} - P-) G^T.
+ *   Two kernels: one wave per (frame, stream) for the gains, one wave per stream for the chain. No atomics, no
+ *   allocation, no host synchronisation: it can follow the tracker on a stream and be stream-captured. */
+typedef struct spef_track_history spef_track_history;
+int spef_track_history_create(spef_track* track, int capacity, spef_track_history** out);
+int spef_track_history_reset(spef_track_history* hist);
+int spef_track_history_count(spef_track_history* hist, int* count_device, void* stream_hip);
+int spef_track_history_push(spef_track_history* hist, spef_track* track, const int* track_status, void* stream_hip);
+/* Copy the rows of frames first .. first + T - 1 to a device buffer of T * n_streams * SPEF_TRACK_STATE_DOUBLES doubles
+ * (first >= 0, T >= 1, first + T <= the frames recorded; SPEF_ERR_ARG otherwise). Enqueued. */
+int spef_track_history_get(spef_track_history* hist, int first, int T, double* out_device, void* stream_hip);
+int spef_track_step_hist(spef_track* track, spef_track_history* hist, const float* quat, const float* pos,
+                         const float* cov, const int* status, int T, int S, float* quat_out, float* pos_out, float* d2,
+                         float* cov_out, float* rates_out, int* track_status, void* stream_hip);
+int spef_track_smooth(spef_track_history* hist, int first, int T, float* quat_io, float* pos_io, float* cov_out,
+                      float* rates_out, int* smooth_status, void* stream_hip);
+int spef_track_history_destroy(spef_track_history* hist);
+
 /* Histogram observers for the INT8 calibration: the statistic of every activation-quantizer input of the float model,
  * accumulated on the device over as many frames as the caller streams (Calibration path;
  * spef_amd.quant.observe_host is the NumPy twin and scales_from_stats turns the counts into scales).

@@ -466,4 +466,139 @@ int spef_track_step_modes(spef_track* tr, const float* mode_quat, const float* m
   return SPEF_OK;
 }
 
+// ------------------------------------------------------------------------------------------ pose smoothing
+struct spef_track_history {
+  spef_track* track = nullptr;   // identity only: the tracker may be gone when the history is smoothed
+  spef_ctx* ctx = nullptr;
+  int device = 0;
+  int S = 0, capacity = 0;
+  int count = 0;                 // frames recorded: known to the host, every launch is sized by it
+  TrackParams prm{};
+  double* rows = nullptr;        // [capacity][S][TRACK_STATE]
+  double* ws = nullptr;          // [capacity][S][SMOOTH_WS]: the backward pass's gains
+};
+
+int spef_track_history_destroy(spef_track_history* h) {
+  if (!h) return SPEF_OK;
+  Dev d(h->device);
+  if (h->rows) hipFree(h->rows);
+  if (h->ws) hipFree(h->ws);
+  delete h;
+  return SPEF_OK;
+}
+
+int spef_track_history_create(spef_track* tr, int capacity, spef_track_history** out) {
+  if (!tr || !out) return fail(SPEF_ERR_ARG, "null argument");
+  if (capacity < 1) return fail(SPEF_ERR_ARG, "capacity must be at least 1");
+  if ((int64_t)capacity * tr->S * 36 > 0x7fffffff)   // the rows of one spef_track_smooth call, as spef_track_step
+    return fail(SPEF_ERR_ARG, "too many rows: capacity * n_streams * 36 must stay below 2^31");
+  Dev d(tr->device);
+  spef_track_history* h = new spef_track_history;
+  h->track = tr;
+  h->ctx = tr->ctx;
+  h->device = tr->device;
+  h->S = tr->S;
+  h->capacity = capacity;
+  h->prm = tr->prm;
+  const size_t rows = (size_t)capacity * tr->S;
+  hipError_t e = hipMalloc(&h->rows, rows * TRACK_STATE * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&h->ws, rows * SMOOTH_WS * sizeof(double));
+  if (e == hipSuccess) e = hipMemset(h->rows, 0, rows * TRACK_STATE * sizeof(double));
+  if (e == hipSuccess) e = hipMemset(h->ws, 0, rows * SMOOTH_WS * sizeof(double));
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    spef_track_history_destroy(h);
+    return fail(SPEF_ERR_HIP, std::string("spef_track_history_create: ") + hipGetErrorString(e));
+  }
+  *out = h;
+  return SPEF_OK;
+}
+
+int spef_track_history_reset(spef_track_history* h) {
+  if (!h) return fail(SPEF_ERR_ARG, "null history");
+  h->count = 0;
+  return SPEF_OK;
+}
+
+int spef_track_history_count(spef_track_history* h, int* count_device, void* stream_hip) {
+  if (!h || !count_device) return fail(SPEF_ERR_ARG, "null argument");
+  Dev d(h->device);
+  HIP_TRY(launch_track_history_count(count_device, h->count, (hipStream_t)stream_hip));
+  return SPEF_OK;
+}
+
+int spef_track_history_push(spef_track_history* h, spef_track* tr, const int* track_status, void* stream_hip) {
+  if (!h || !tr || !track_status) return fail(SPEF_ERR_ARG, "null argument");
+  if (h->track != tr || h->S != tr->S) return fail(SPEF_ERR_ARG, "the history belongs to another tracker");
+  if (h->count + 1 > h->capacity) return fail(SPEF_ERR_ARG, "the history is full");
+  Dev d(h->device);
+  HIP_TRY(launch_track_history_push(h->rows + (int64_t)h->count * h->S * TRACK_STATE, tr->state, track_status, h->S,
+                                    (hipStream_t)stream_hip));
+  h->count += 1;
+  return SPEF_OK;
+}
+
+int spef_track_history_get(spef_track_history* h, int first, int T, double* out_device, void* stream_hip) {
+  if (!h || !out_device) return fail(SPEF_ERR_ARG, "null argument");
+  if (first < 0 || T < 1 || (int64_t)first + T > h->count) return fail(SPEF_ERR_ARG, "frames out of range");
+  Dev d(h->device);
+  HIP_TRY(launch_track_copy(out_device, h->rows + (int64_t)first * h->S * TRACK_STATE, (int64_t)T * h->S * TRACK_STATE,
+                            (hipStream_t)stream_hip));
+  return SPEF_OK;
+}
+
+int spef_track_step_hist(spef_track* tr, spef_track_history* h, const float* quat, const float* pos, const float* cov,
+                         const int* status, int T, int S, float* quat_out, float* pos_out, float* d2, float* cov_out,
+                         float* rates_out, int* track_status, void* stream_hip) {
+  if (!tr || !h) return fail(SPEF_ERR_ARG, "null tracker or history");
+  if (!quat || !pos || !quat_out || !pos_out || !track_status) return fail(SPEF_ERR_ARG, "null argument");
+  if (h->track != tr || h->S != tr->S) return fail(SPEF_ERR_ARG, "the history belongs to another tracker");
+  if (S != tr->S)
+    return fail(SPEF_ERR_ARG, "S = " + std::to_string(S) + ", the tracker has " + std::to_string(tr->S) + " streams");
+  if (T < 1) return fail(SPEF_ERR_ARG, "T must be at least 1");
+  if ((int64_t)T * S * 36 > 0x7fffffff) return fail(SPEF_ERR_ARG, "too many rows");
+  if ((int64_t)h->count + T > h->capacity)
+    return fail(SPEF_ERR_ARG, std::to_string(h->count) + " + " + std::to_string(T) + " frames exceed the history's capacity " +
+                                  std::to_string(h->capacity));
+  spef_ctx* c = tr->ctx;
+  Dev d(tr->device);
+  hipStream_t s = (hipStream_t)stream_hip;
+  const double rows = (double)T * S;
+  HIP_TRY(prof_launch(c, s, "track_step_hist_kernel",
+                      rows * (2 * 28 + 8 + (cov ? 144 : 0) + (status ? 4 : 0) + (cov_out ? 144 : 0) + (rates_out ? 24 : 0) +
+                              TRACK_STATE * 8) +
+                          2.0 * S * TRACK_STATE * 8,
+                      rows * 2.0 * 3000.0, [&] {
+    return launch_track_step_hist(tr->prm, tr->state, h->rows + (int64_t)h->count * S * TRACK_STATE, quat, pos, cov,
+                                  status, T, S, quat_out, pos_out, d2, cov_out, rates_out, track_status, s);
+  }));
+  h->count += T;
+  return SPEF_OK;
+}
+
+int spef_track_smooth(spef_track_history* h, int first, int T, float* quat_io, float* pos_io, float* cov_out,
+                      float* rates_out, int* smooth_status, void* stream_hip) {
+  if (!h) return fail(SPEF_ERR_ARG, "null history");
+  if (!quat_io || !pos_io || !smooth_status) return fail(SPEF_ERR_ARG, "null argument");
+  if (first < 0 || T < 1 || (int64_t)first + T > h->count)
+    return fail(SPEF_ERR_ARG, "frames " + std::to_string(first) + " .. " + std::to_string((int64_t)first + T - 1) +
+                                  " are not all recorded (" + std::to_string(h->count) + " frames)");
+  spef_ctx* c = h->ctx;
+  Dev d(h->device);
+  hipStream_t s = (hipStream_t)stream_hip;
+  const int S = h->S;
+  const double rows = (double)T * S;
+  const double* x = h->rows + (int64_t)first * S * TRACK_STATE;
+  double* ws = h->ws + (int64_t)first * S * SMOOTH_WS;
+  const bool want_cov = cov_out != nullptr;
+  HIP_TRY(prof_launch(c, s, "smooth_gain_kernel", rows * 8.0 * (TRACK_STATE + 152 + (want_cov ? 144 : 0)),
+                      rows * 2.0 * 1500.0, [&] { return launch_track_smooth_gain(h->prm, x, ws, T, S, want_cov, s); }));
+  HIP_TRY(prof_launch(c, s, "smooth_chain_kernel",
+                      rows * (8.0 * (16 + 152 + (want_cov ? 288 : 0)) + 28 + 4 + (want_cov ? 144 : 0) + (rates_out ? 24 : 0)),
+                      rows * 2.0 * (want_cov ? 3700.0 : 250.0), [&] {
+    return launch_track_smooth_chain(x, ws, T, S, quat_io, pos_io, cov_out, rates_out, smooth_status, s);
+  }));
+  return SPEF_OK;
+}
+
 }  // extern "C"

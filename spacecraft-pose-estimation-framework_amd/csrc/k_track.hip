@@ -14,55 +14,9 @@
 #include "spef_common.hpp"
 #include "spef_kernels.hpp"
 #include "spef_pose_math.hpp"
+#include "spef_track_math.hpp"
 
 namespace spef {
-
-enum : int { TS_INVALID = 1, TS_GATED = 2, TS_REINIT = 4, TS_NO_TRACK = 8 };
-
-// Hamilton product, scalar first: R(a (x) b) = R(a) R(b)
-__device__ __forceinline__ void track_qmul(const double (&a)[4], const double (&b)[4], double (&o)[4]) {
-  o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-  o[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-  o[2] = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
-  o[3] = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
-}
-
-// the quaternion of the rotation vector w (series below |w|^2 = 1e-16)
-__device__ __forceinline__ void track_qexp(const double (&w)[3], double (&o)[4]) {
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-  double c = 1.0 - th2 / 8.0, s = 0.5 - th2 / 48.0;
-  if (!(th2 < 1e-16)) {
-    const double th = dsqrt(th2);
-    double sh;
-    sincos(0.5 * th, &sh, &c);
-    s = sh * rcp_nr(th);
-  }
-  o[0] = c;
-  o[1] = s * w[0];
-  o[2] = s * w[1];
-  o[3] = s * w[2];
-}
-
-__device__ __forceinline__ void track_unit(double (&q)[4]) {
-  const double inv = rsq_nr(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] *= inv;
-}
-
-// o = exp(w) (x) q, normalised, in the hemisphere of ref
-__device__ __forceinline__ void track_rotate(const double (&w)[3], const double (&q)[4], const double (&ref)[4],
-                                             double (&o)[4]) {
-  double e[4];
-  track_qexp(w, e);
-  track_qmul(e, q, o);
-  track_unit(o);
-  if (o[0] * ref[0] + o[1] * ref[1] + o[2] * ref[2] + o[3] * ref[3] < 0.0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = -o[k];
-  }
-}
-
-__device__ __forceinline__ bool track_finite(double x) { return fabs(x) < INFINITY; }
 
 // Step 4 of spe/track.py for one measurement (q_m, t_m) against the prediction (q-, t-, P- in LDS): the innovation y, R
 // from the row's covariance (cov_at(i, j), used when have_cov and all 36 entries are finite; diag(r) otherwise),
@@ -669,6 +623,291 @@ __global__ __launch_bounds__(64) void track_step_modes_kernel(TrackParams prm, d
   for (int e = lane; e < 144; e += 64) st[16 + e] = sP[e];
 }
 
+// spef_track_step_hist: track_step_kernel with the posterior of every frame recorded for the smoother (k_smooth.hip) --
+// the state row as spef_track_get_state lays it out, with the frame's track status in slot 2, at hist[row]. It is
+// track_step_kernel's text and one store per frame, a kernel of its own for the reason given above
+// (tests/test_gpu_smooth.py holds the two against each other bit for bit, outputs and fp64 state).
+__global__ __launch_bounds__(64) void track_step_hist_kernel(TrackParams prm, double* __restrict__ state,
+                                                             double* __restrict__ hist, const float* quat,
+                                                             const float* pos, const float* __restrict__ cov,
+                                                             const int* __restrict__ status, int T, int S,
+                                                             float* quat_out, float* pos_out,
+                                                             float* __restrict__ d2_out, float* __restrict__ cov_out,
+                                                             float* __restrict__ rates_out,
+                                                             int* __restrict__ track_status) {
+  __shared__ double sP[144], sPm[144], sW[72], sD[12];
+  const int s = blockIdx.x, lane = threadIdx.x;
+  if (s >= S) return;   // uniform per wave
+  double* st = state + (size_t)s * TRACK_STATE;
+  double have = st[0], coast = st[1];
+  double q[4], t[3], w[3], v[3];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) q[k] = st[3 + k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    t[k] = st[7 + k];
+    w[k] = st[10 + k];
+    v[k] = st[13 + k];
+  }
+  for (int e = lane; e < 144; e += 64) sP[e] = st[16 + e];
+  __syncthreads();
+
+  for (int f = 0; f < T; ++f) {
+    const size_t row = (size_t)f * S + s;
+    // ---- measurement (every lane reads the same words: a broadcast)
+    float qf[4], tf[3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) qf[k] = quat[4 * row + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tf[k] = pos[3 * row + k];
+    const int dst = status ? status[row] : 0;
+    double qm[4], tm[3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) qm[k] = (double)qf[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tm[k] = (double)tf[k];
+    const double qn2 = qm[0] * qm[0] + qm[1] * qm[1] + qm[2] * qm[2] + qm[3] * qm[3];
+    const bool valid = (dst & 15) == 0 && qn2 > 0.0 && qn2 < INFINITY && track_finite(tm[0]) && track_finite(tm[1]) &&
+                       track_finite(tm[2]);   // a NaN or an infinity in q_m makes qn2 NaN or infinite
+    int ts = 0;
+    double d2 = NAN;
+    bool start = false;   // start the track (again) from this measurement
+    bool pass = false;    // no track and nothing to start one from: the row goes through as it came
+
+    if (have == 0.0) {
+      if (valid) {
+        start = true;
+        d2 = 0.0;
+      } else {
+        pass = true;
+        ts = TS_INVALID | TS_NO_TRACK;
+      }
+    } else {
+      // ---- predict: P- = F P F^T + Q, F = [[I, I], [0, I]]; lane e owns entries e, e + 64, e + 128
+      for (int e = lane; e < 144; e += 64) {
+        const int i = e / 12, j = e - 12 * i;
+        double p;
+        if (i < 6 && j < 6) {
+          p = ((sP[12 * i + j] + (sP[12 * i + 6 + j] + sP[12 * j + 6 + i])) + sP[12 * (i + 6) + 6 + j]) +
+              (i == j ? prm.q[i / 3] : 0.0);
+        } else if (i < 6) {
+          p = sP[12 * i + j] + sP[12 * (i + 6) + j];
+        } else if (j < 6) {
+          p = sP[12 * j + i] + sP[12 * (j + 6) + i];
+        } else {
+          p = sP[e] + (i == j ? prm.q[i / 3] : 0.0);
+        }
+        sPm[e] = p;
+      }
+      double qp[4], tp[3];
+      track_rotate(w, q, q, qp);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) tp[k] = t[k] + v[k];
+      __syncthreads();
+
+      // ---- innovation, S = P-[0:6, 0:6] + R = L L^T, z = L^-1 y, d2 = z^T z (uniform on every lane)
+      bool ok = false;
+      double L[6][6], inv[6], z[6];
+      if (valid) {
+        double R[6][6];
+        bool use_cov = cov != nullptr;
+        if (use_cov) {
+          double c[6][6];
+#pragma unroll
+          for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+              c[i][j] = (double)cov[36 * row + 6 * i + j];
+              use_cov = use_cov && track_finite(c[i][j]);
+            }
+#pragma unroll
+          for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) R[i][j] = prm.cov_scale * ((c[i][j] + c[j][i]) * 0.5);
+        }
+        if (!use_cov) {
+#pragma unroll
+          for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) R[i][j] = i == j ? prm.r[i / 3] : 0.0;
+        }
+        double qu[4] = {qm[0], qm[1], qm[2], qm[3]};
+        track_unit(qu);
+        const double qc[4] = {qp[0], -qp[1], -qp[2], -qp[3]};
+        double d[4];
+        track_qmul(qu, qc, d);
+        if (d[0] < 0.0) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) d[k] = -d[k];
+        }
+        const double n2 = d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
+        const double n = dsqrt(n2);
+        const double fl = n < 1e-8 ? 2.0 / d[0] * (1.0 - n2 / (3.0 * d[0] * d[0])) : 2.0 * atan2(n, d[0]) * rcp_nr(n);
+        const double y[6] = {fl * d[1], fl * d[2], fl * d[3], tm[0] - tp[0], tm[1] - tp[1], tm[2] - tp[2]};
+        ok = true;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          double dd = sPm[12 * j + j] + R[j][j];
+#pragma unroll
+          for (int k = 0; k < j; ++k) dd -= L[j][k] * L[j][k];
+          const bool good = dd > 0.0 && dd < INFINITY;
+          ok = ok && good;
+          dd = good ? dd : 1.0;
+          inv[j] = rsq_nr(dd);
+          L[j][j] = dd * inv[j];
+#pragma unroll
+          for (int i = j + 1; i < 6; ++i) {
+            double a = sPm[12 * i + j] + R[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) a -= L[i][k] * L[j][k];
+            L[i][j] = a * inv[j];
+          }
+        }
+        if (ok) {
+          d2 = 0.0;
+#pragma unroll
+          for (int i = 0; i < 6; ++i) {
+            double a = y[i];
+#pragma unroll
+            for (int k = 0; k < i; ++k) a -= L[i][k] * z[k];
+            z[i] = a * inv[i];
+          }
+#pragma unroll
+          for (int k = 0; k < 6; ++k) d2 += z[k] * z[k];
+        }
+      }
+      if (!ok) {
+        ts = TS_INVALID;
+      } else if (prm.gate_chi2 > 0.0 && d2 > prm.gate_chi2) {
+        ts = TS_GATED;
+      }
+
+      if (ts != 0) {
+        if (ts == TS_GATED && coast + 1.0 > prm.max_coast) {
+          start = true;
+          ts = TS_GATED | TS_REINIT;
+        } else {   // coast: the state becomes the prediction, w and v are kept
+          coast += 1.0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) q[k] = qp[k];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) t[k] = tp[k];
+          for (int e = lane; e < 144; e += 64) sP[e] = sPm[e];   // the entries this lane wrote
+        }
+      } else {
+        // ---- update through the factor: W = P-[:, 0:6] L^-T (K = W L^-1, K S K^T = W W^T), delta = W z
+        if (lane < 12) {
+          double wr[6], dl = 0.0;
+#pragma unroll
+          for (int k = 0; k < 6; ++k) {
+            double a = sPm[12 * lane + k];
+#pragma unroll
+            for (int m = 0; m < k; ++m) a -= wr[m] * L[k][m];
+            wr[k] = a * inv[k];
+            sW[6 * lane + k] = wr[k];
+          }
+#pragma unroll
+          for (int k = 0; k < 6; ++k) dl += wr[k] * z[k];
+          sD[lane] = dl;
+        }
+        __syncthreads();
+        for (int e = lane; e < 144; e += 64) {
+          const int i = e / 12, j = e - 12 * i;
+          double p = sPm[e];
+#pragma unroll
+          for (int k = 0; k < 6; ++k) p -= sW[6 * i + k] * sW[6 * j + k];
+          sP[e] = p;
+        }
+        const double dth[3] = {sD[0], sD[1], sD[2]};
+        double qn[4];
+        track_rotate(dth, qp, q, qn);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = qn[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          t[k] = tp[k] + sD[3 + k];
+          w[k] += sD[6 + k];
+          v[k] += sD[9 + k];
+        }
+        coast = 0.0;
+      }
+    }
+
+    if (start) {   // q = q_m / |q_m| (in the previous output's hemisphere when there was one), w = v = 0, P = diag(p0)
+      double qs[4] = {qm[0], qm[1], qm[2], qm[3]};
+      track_unit(qs);
+      const bool flip = have != 0.0 && qs[0] * q[0] + qs[1] * q[1] + qs[2] * q[2] + qs[3] * q[3] < 0.0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) q[k] = flip ? -qs[k] : qs[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        t[k] = tm[k];
+        w[k] = 0.0;
+        v[k] = 0.0;
+      }
+      for (int e = lane; e < 144; e += 64) {
+        const int i = e / 12, j = e - 12 * i;
+        sP[e] = i == j ? prm.p0[i / 3] : 0.0;
+      }
+      have = 1.0;
+      coast = 0.0;
+    }
+    __syncthreads();   // P of this frame is complete
+
+    // ---- outputs
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) quat_out[4 * row + k] = pass ? qf[k] : (float)q[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) pos_out[3 * row + k] = pass ? tf[k] : (float)t[k];
+      if (d2_out) d2_out[row] = (float)d2;
+      track_status[row] = ts;
+    }
+    if (rates_out && lane < 6) {
+      const double rv = lane == 0 ? w[0] : lane == 1 ? w[1] : lane == 2 ? w[2] : lane == 3 ? v[0] : lane == 4 ? v[1] : v[2];
+      rates_out[6 * row + lane] = pass ? NAN : (float)rv;
+    }
+    if (cov_out && lane < 36) {
+      const int i = lane / 6, j = lane - 6 * i;
+      cov_out[36 * row + lane] = pass ? NAN : (float)sP[12 * i + j];
+    }
+
+    // ---- the posterior of this frame for the smoother: the state row, the track status in slot 2
+    // (staging the 16 scalars through LDS for three wide stores instead of sixteen by one lane measured slower)
+    double* hr = hist + row * TRACK_STATE;
+    if (lane == 0) {
+      hr[0] = have;
+      hr[1] = coast;
+      hr[2] = (double)ts;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) hr[3 + k] = q[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        hr[7 + k] = t[k];
+        hr[10 + k] = w[k];
+        hr[13 + k] = v[k];
+      }
+    }
+    for (int e = lane; e < 144; e += 64) hr[16 + e] = sP[e];
+  }
+
+  // ---- the state goes back as fp64: the next call continues bit for bit
+  if (lane == 0) {
+    st[0] = have;
+    st[1] = coast;
+    st[2] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) st[3 + k] = q[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      st[7 + k] = t[k];
+      st[10 + k] = w[k];
+      st[13 + k] = v[k];
+    }
+  }
+  for (int e = lane; e < 144; e += 64) st[16 + e] = sP[e];
+}
+
 __global__ __launch_bounds__(256) void track_reset_kernel(double* __restrict__ state, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) state[i] = 0.0;
 }
@@ -685,6 +924,15 @@ hipError_t launch_track_step(const TrackParams& p, double* state, const float* q
                              float* d2, float* cov_out, float* rates_out, int* track_status, hipStream_t s) {
   track_step_kernel<<<S, 64, 0, s>>>(p, state, quat, pos, cov, status, T, S, quat_out, pos_out, d2, cov_out, rates_out,
                                      track_status);
+  return hipGetLastError();
+}
+
+hipError_t launch_track_step_hist(const TrackParams& p, double* state, double* hist, const float* quat,
+                                  const float* pos, const float* cov, const int* status, int T, int S, float* quat_out,
+                                  float* pos_out, float* d2, float* cov_out, float* rates_out, int* track_status,
+                                  hipStream_t s) {
+  track_step_hist_kernel<<<S, 64, 0, s>>>(p, state, hist, quat, pos, cov, status, T, S, quat_out, pos_out, d2, cov_out,
+                                          rates_out, track_status);
   return hipGetLastError();
 }
 

@@ -300,6 +300,29 @@ hipError_t launch_track_step_modes(const TrackParams& p, double* state, const fl
 // Zero n doubles at state (a stream without a track); copy n doubles (get / set state).
 hipError_t launch_track_reset(double* state, int64_t n, hipStream_t s);
 hipError_t launch_track_copy(double* dst, const double* src, int64_t n, hipStream_t s);
+// launch_track_step that also records the posterior of frame f of stream s at hist[(f * S + s) * TRACK_STATE]: the
+// state row with the frame's track status in slot 2 (hist points at the first frame of the call).
+hipError_t launch_track_step_hist(const TrackParams& p, double* state, double* hist, const float* quat,
+                                  const float* pos, const float* cov, const int* status, int T, int S, float* quat_out,
+                                  float* pos_out, float* d2, float* cov_out, float* rates_out, int* track_status,
+                                  hipStream_t s);
+
+// ---- pose smoothing (k_smooth.hip; the arithmetic is stated in spef_amd/spe/smooth.py) ----
+// A workspace row of the backward pass, per history row: ok (1 / 0: P- of the next frame has a Cholesky factor),
+// q-[4], t-[3], the gain G[144] and P-[144], row-major.
+constexpr int SMOOTH_WS = 296;
+// One frame of S history rows from the tracker's state and track_status [S].
+hipError_t launch_track_history_push(double* hist_frame, const double* state, const int* track_status, int S,
+                                     hipStream_t s);
+hipError_t launch_track_history_count(int* out, int count, hipStream_t s);
+// The backward pass over T frames of S streams; hist and ws point at the window's first frame. quat_io [T*S][4] and
+// pos_io [T*S][3] hold the filter's outputs and receive the smoothed pose; cov_out [T*S][36] and rates_out [T*S][6]
+// may be null (without cov_out no covariance is smoothed). Two launches: the gains, one wave per row of the first
+// T - 1 frames, and the chains, one wave per stream.
+hipError_t launch_track_smooth_gain(const TrackParams& p, const double* hist, double* ws, int T, int S, bool want_cov,
+                                    hipStream_t s);
+hipError_t launch_track_smooth_chain(const double* hist, const double* ws, int T, int S, float* quat_io, float* pos_io,
+                                     float* cov_out, float* rates_out, int* smooth_status, hipStream_t s);
 
 // ---- histogram observers of the INT8 calibration (k_observe.hip) ----
 constexpr int OBS_BINS = 8192, OBS_COUNTERS = 8;   // one tap's record: OBS_COUNTERS + OBS_BINS uint64

@@ -63,6 +63,14 @@ SIGNATURES = {
     'spef_track_step_modes': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp]),
     'spef_track_destroy': (_i, [_vp]),
+    'spef_track_history_create': (_i, [_vp, _i, C.POINTER(_vp)]),
+    'spef_track_history_reset': (_i, [_vp]),
+    'spef_track_history_count': (_i, [_vp, _vp, _vp]),
+    'spef_track_history_push': (_i, [_vp, _vp, _vp, _vp]),
+    'spef_track_history_get': (_i, [_vp, _i, _i, _vp, _vp]),
+    'spef_track_step_hist': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'spef_track_smooth': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'spef_track_history_destroy': (_i, [_vp]),
     'spef_observer_create': (_i, [_vp, C.POINTER(_vp)]),
     'spef_observer_info': (_i, [_vp, _ip, _ip]),
     'spef_observer_reset': (_i, [_vp, _vp]),

@@ -227,14 +227,20 @@ class PoseTracker:
         self.handle = h
         self.last_event = None   # StreamPipeline: the event after the last step it enqueued (steps serialise)
 
+    def history(self, capacity: int) -> 'PoseHistory':
+        """A device buffer for the posteriors of up to ``capacity`` frames of every stream: what ``step(...,
+        history=h)`` / ``PoseHistory.push`` record and ``PoseHistory.smooth`` runs the backward pass over."""
+        return PoseHistory(self, capacity)
+
     def step(self, dec: dict, T: int, engine: Optional['Engine'] = None, want_cov: bool = False,
-             want_rates: bool = False) -> dict:
+             want_rates: bool = False, history: Optional['PoseHistory'] = None) -> dict:
         """``dec``: a decode dict of ``T * n_streams`` time-major rows: 'ori', 'pos', and when present 'status' (the
         decode status: rows with any of bits 1 | 2 | 4 | 8 are coasted over) and 'cov' ([B x 6 x 6], the pose
         covariance of ``decode_keypoints(want_cov=True)`` or of ``decode_cov``). -> {'ori', 'pos', 'mahalanobis', 'track_status'} and, when
         asked for, 'cov' [B x 6 x 6] (the pose block of P) and 'rates' [B x 6] (w, v) -- device tensors; the inputs are
         left as they are. ``engine`` is accepted for symmetry with ``VideoFilter.step``; the tracker needs no
-        tables."""
+        tables. With ``history`` (``self.history(capacity)``) the T frames are also recorded for
+        ``PoseHistory.smooth``; outputs and state are the same bit for bit."""
         quat, pos, status, cov = dec['ori'], dec['pos'], dec.get('status'), dec.get('cov')
         B, S, dev = quat.shape[0], self.n_streams, self.device
         assert T >= 1 and B == T * S, f'{B} rows are not T = {T} steps of {S} streams'
@@ -252,8 +258,15 @@ class PoseTracker:
         ts = torch.empty((B,), dtype=torch.int32, device=dev)
         co = torch.empty((B, 6, 6), dtype=torch.float32, device=dev) if want_cov else None
         ro = torch.empty((B, 6), dtype=torch.float32, device=dev) if want_rates else None
-        L.check(self.lib.spef_track_step(self.handle, _ptr(quat), _ptr(pos), _ptr(cov), _ptr(status), T, S, _ptr(qo),
-                                         _ptr(po), _ptr(d2), _ptr(co), _ptr(ro), _ptr(ts), _stream(dev)))
+        if history is None:
+            L.check(self.lib.spef_track_step(self.handle, _ptr(quat), _ptr(pos), _ptr(cov), _ptr(status), T, S,
+                                             _ptr(qo), _ptr(po), _ptr(d2), _ptr(co), _ptr(ro), _ptr(ts), _stream(dev)))
+        else:   # the same step, bit for bit, with the posterior of every frame appended to ``history``
+            assert history.tracker is self, 'the history belongs to another tracker'
+            L.check(self.lib.spef_track_step_hist(self.handle, history.handle, _ptr(quat), _ptr(pos), _ptr(cov),
+                                                  _ptr(status), T, S, _ptr(qo), _ptr(po), _ptr(d2), _ptr(co),
+                                                  _ptr(ro), _ptr(ts), _stream(dev)))
+            history.count += T
         out = {'ori': qo, 'pos': po, 'mahalanobis': d2, 'track_status': ts}
         if want_cov:
             out['cov'] = co
@@ -323,6 +336,93 @@ class PoseTracker:
         if getattr(self, 'handle', None):
             torch.cuda.synchronize(self.device)
             self.lib.spef_track_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PoseHistory:
+    """The posteriors of up to ``capacity`` frames of every stream of a ``PoseTracker`` on the device
+    (``PoseTracker.history``), and the fixed-interval smoother over them (csrc/k_smooth.hip; every step is stated in
+    ``spef_amd.spe.smooth``): a Rauch-Tung-Striebel backward pass, so that a recorded video's frame k is estimated
+    from every frame of the window. Frames are recorded by ``PoseTracker.step(..., history=self)`` or, after
+    ``step_modes`` or live T = 1 steps, by ``push``. ``count`` is the number of frames recorded (kept on the host).
+    Nothing here allocates in the library or synchronises after creation."""
+
+    def __init__(self, tracker: PoseTracker, capacity: int):
+        self.tracker = tracker
+        self.lib = tracker.lib
+        self.device = tracker.device
+        self.n_streams = tracker.n_streams
+        self.capacity = int(capacity)
+        self.count = 0
+        h = C.c_void_p()
+        L.check(self.lib.spef_track_history_create(tracker.handle, self.capacity, C.byref(h)))
+        self.handle = h
+
+    def reset(self) -> None:
+        """Forget every recorded frame."""
+        L.check(self.lib.spef_track_history_reset(self.handle))
+        self.count = 0
+
+    def push(self, track_status: torch.Tensor) -> None:
+        """Append the tracker's current state as one more frame; ``track_status`` [n_streams] int32 is the
+        'track_status' of the step that produced it (one copy kernel on the current stream)."""
+        assert track_status.device == self.device and track_status.dtype == torch.int32
+        assert track_status.numel() == self.n_streams and track_status.is_contiguous()
+        L.check(self.lib.spef_track_history_push(self.handle, self.tracker.handle, _ptr(track_status),
+                                                 _stream(self.device)))
+        self.count += 1
+
+    def device_count(self) -> torch.Tensor:
+        """The number of frames recorded as a device int32 scalar (enqueued on the current stream)."""
+        out = torch.empty((), dtype=torch.int32, device=self.device)
+        L.check(self.lib.spef_track_history_count(self.handle, _ptr(out), _stream(self.device)))
+        return out
+
+    def smooth(self, out: dict, first: int = 0, T: Optional[int] = None, want_cov: bool = False,
+               want_rates: bool = False) -> dict:
+        """``out``: the tracker's outputs ('ori', 'pos') for the ``T * n_streams`` time-major rows of frames
+        ``first .. first + T - 1`` (``T`` None: every frame recorded from ``first`` on). -> {'ori', 'pos',
+        'smooth_status'} and, when asked for, 'cov' [B x 6 x 6] (the pose block of P^s) and 'rates' [B x 6] -- new device
+        tensors; ``out`` is left as it is. 'smooth_status': 0 smoothed, 1 no track (the row is ``out``'s, 'cov' and
+        'rates' NaN), 2 a chain ends here and the row is the filter's (with 4: P- had no Cholesky factor). Two kernels
+        on the current stream; without ``want_cov`` no covariance is smoothed."""
+        T = self.count - int(first) if T is None else int(T)
+        B, dev = T * self.n_streams, self.device
+        quat, pos = out['ori'], out['pos']
+        assert T >= 1 and quat.shape == (B, 4) and pos.shape == (B, 3), f'{tuple(quat.shape)} is not T = {T} frames'
+        for t in (quat, pos):
+            assert t.device == dev and t.dtype == torch.float32
+        qo, po = quat.clone(memory_format=torch.contiguous_format), pos.clone(memory_format=torch.contiguous_format)
+        ss = torch.empty((B,), dtype=torch.int32, device=dev)
+        co = torch.empty((B, 6, 6), dtype=torch.float32, device=dev) if want_cov else None
+        ro = torch.empty((B, 6), dtype=torch.float32, device=dev) if want_rates else None
+        L.check(self.lib.spef_track_smooth(self.handle, int(first), T, _ptr(qo), _ptr(po), _ptr(co), _ptr(ro), _ptr(ss),
+                                           _stream(dev)))
+        res = {'ori': qo, 'pos': po, 'smooth_status': ss}
+        if want_cov:
+            res['cov'] = co
+        if want_rates:
+            res['rates'] = ro
+        return res
+
+    def rows(self, first: int = 0, T: Optional[int] = None) -> torch.Tensor:
+        """The recorded rows of frames ``first .. first + T - 1`` as a float64 device tensor [T, n_streams, 160]: the
+        tracker's state after each frame (``PoseTracker.state``'s layout) with the frame's track status in slot 2."""
+        T = self.count - int(first) if T is None else int(T)
+        out = torch.empty((max(T, 0), self.n_streams, L.TRACK_STATE_DOUBLES), dtype=torch.float64, device=self.device)
+        L.check(self.lib.spef_track_history_get(self.handle, int(first), T, _ptr(out), _stream(self.device)))
+        return out
+
+    def close(self) -> None:
+        if getattr(self, 'handle', None):
+            torch.cuda.synchronize(self.device)
+            self.lib.spef_track_history_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

@@ -22,6 +22,10 @@ pose of any head, keypoint mode included, with the device tracker (csrc/k_track.
 (off by default) makes the measurement covariance that of the soft-classification PDFs (``Engine.decode_cov``).
 ``Inference.tracker_modes = K`` (0 by default) keeps up to K orientations of an ambiguous orientation PDF per frame
 (``Engine.decode_modes``) and lets the tracker pick among them; the still pose then carries 'modes'.
+
+``video_type='Smoother'`` (``predict_sequence`` only: a recorded video) is the tracker followed by a fixed-interval
+smoother over the T frames of the call (csrc/k_smooth.hip, ``PoseHistory.smooth``): ``pose_video`` is the smoothed pose
+and also has 'smooth_status'. ``predict`` raises ValueError for it: a single frame has nothing to smooth.
 """
 from __future__ import annotations
 
@@ -146,19 +150,22 @@ class Inference:
                 self.prev_still_ori = ori[t]
         return ori
 
-    def _tracked(self, images: torch.Tensor) -> list:
+    def _tracked(self, images: torch.Tensor, smooth: bool = False) -> list:
         """video_type 'Tracker' for T consecutive frames of one video: one batched forward, one decode and one
         tracker step on the GPU (``SPEMi355x.predict_tracked``, one stream; the state stays in the device tracker, so
         any cut of a video into calls gives the same poses). -> T triples (pose_still, latency_ms, pose_video) with
         pose_video = {'ori', 'pos', 'mahalanobis', 'track_status', 'keypoints', 'bbox'}; in keypoint mode its
-        'keypoints' are the reprojection of the tracked pose."""
+        'keypoints' are the reprojection of the tracked pose. With ``smooth`` (video_type 'Smoother') the pose is the
+        fixed-interval smoother's over these T frames and pose_video also has 'smooth_status'."""
         eng, su = self.inference_engine, self.spe_utils
         if not hasattr(eng, 'predict_tracked'):
             raise ValueError("video filtering 'Tracker' needs the 'gpu_mi355x' engine")
         T = int(images.shape[0])
         pdf_cov = {'pdf_cov': True} if self.tracker_pdf_cov else {}
         modes = {'modes': int(self.tracker_modes)} if self.tracker_modes else {}
-        still, tracked, latency_ms = eng.predict_tracked(images, 1, **pdf_cov, **modes, **self.tracker_params)
+        smoothing = {'smooth': True} if smooth else {}
+        still, tracked, latency_ms = eng.predict_tracked(images, 1, **pdf_cov, **modes, **smoothing,
+                                                         **self.tracker_params)
         still = dict(still)
         still['ori'] = self._still_pole(still['ori'])
         found = still.pop('modes', None)     # tracker_modes: a dict of per-frame arrays
@@ -192,9 +199,9 @@ class Inference:
         step and read back after it, so ``reset()`` clears both and the two calls can be mixed on one video.
         An engine without ``predict_video`` (one of the reference's own, through ``engine_factories``) is driven
         frame by frame."""
-        if video_type == 'Tracker':
+        if video_type in ('Tracker', 'Smoother'):   # 'Smoother': the tracker and a backward pass over these T frames
             self.img_size = (1,) + tuple(images.size())[1:]
-            return self._tracked(images)
+            return self._tracked(images, smooth=video_type == 'Smoother')
         if video_type is not None and video_type != 'Adaptative':
             raise ValueError(f'type of video filtering not implemented: {video_type}')
         eng = self.inference_engine
@@ -246,6 +253,9 @@ class Inference:
         """inference.py:117-191: -> (pose of the still frame, latency ms, filtered video pose or None)."""
         if not self.img_size or self.img_size != tuple(image.size()):
             self.img_size = tuple(image.size())
+        if video_type == 'Smoother':
+            raise ValueError("video filtering 'Smoother' needs a recorded sequence (predict_sequence): a single frame "
+                             'has nothing to smooth')
         if video_type == 'Tracker':      # the pose tracker (any head): still and tracked pose from one device pass
             return self._tracked(image)[0]
         pose_still, latency_ms = self.inference_engine.predict(image)

@@ -248,14 +248,26 @@ class SPEMi355x:
             self._track = (key, self.engine.tracker(n_streams, **params))
         return self._track[1]
 
+    def _history(self, trk, capacity: int):
+        """The ``PoseHistory`` of ``predict_tracked(smooth=True)``: kept with the tracker, grown when a call is longer."""
+        h = getattr(self, '_hist', None)
+        if h is None or h.tracker is not trk or h.capacity < capacity:
+            if h is not None:
+                h.close()
+            self._hist = h = trk.history(capacity)
+        return h
+
     def _close_track(self) -> None:
+        if getattr(self, '_hist', None) is not None:
+            self._hist.close()
+        self._hist = None
         if getattr(self, '_track', None) is not None:
             self._track[1].close()
         self._track = None
 
     def predict_tracked(self, images: torch.Tensor, n_streams: int = 1, targets=None, scorer=None,
                         pdf_cov: bool = False, floor_var=(0.0, 0.0), modes: int = 0, modes_params=None,
-                        **params) -> Tuple[Dict, Dict, float]:
+                        smooth: bool = False, **params) -> Tuple[Dict, Dict, float]:
         """Time-major video frames ``images`` [T * n_streams, ...] (row t * n_streams + s = step t of stream s) ->
         (still pose, tracked pose, latency ms) for every head mode: one batched forward, one decode and one tracker
         step (``Engine.tracker``: an error-state Kalman filter with gating and coasting), all on the GPU. The still
@@ -275,7 +287,13 @@ class SPEMi355x:
         orientation head (AssertionError otherwise).
         The tracker's state persists between calls (``tracker(...).reset()`` starts new videos). ``params``: as
         ``Engine.tracker``. With ``targets`` and ``scorer`` (``engine.scorer(n_streams, 2, capacity)``) track 0 logs the
-        still poses and track 1 the tracked ones; a tracked row counts as failed only where it passed through."""
+        still poses and track 1 the tracked ones; a tracked row counts as failed only where it passed through.
+        ``smooth=True`` (a recorded video): the posteriors of the call's T frames are recorded on the device and a
+        fixed-interval smoother (``PoseHistory.smooth``: a Rauch-Tung-Striebel backward pass; the window is this call)
+        replaces 'ori' and 'pos' of the tracked pose by the smoothed ones, adds 'smooth_status' and is what a scorer
+        scores as track 1; 'mahalanobis' and 'track_status' stay the filter's, and so does the tracker's state. With
+        ``modes=K`` the frames are recorded through ``PoseHistory.push``, one ``step_modes`` per time step (the same
+        track bit for bit: a stream's result does not depend on how its frames are cut into calls)."""
         if self.engine is None:
             raise AssertionError('no model loaded')
         x = images.to(self.device, non_blocking=True).contiguous()
@@ -305,7 +323,24 @@ class SPEMi355x:
                                      floor_var=floor_var)
         else:
             dec = self.engine.decode(self.ori_mode, self.pos_mode, raw0, raw1)
-        out = trk.step_modes(dec, B // n_streams) if modes else trk.step(dec, B // n_streams)
+        T = B // n_streams
+        if not smooth:
+            out = trk.step_modes(dec, T) if modes else trk.step(dec, T)
+        else:
+            hist = self._history(trk, T)
+            hist.reset()
+            if modes:
+                keys = [k for k, v in dec.items() if isinstance(v, torch.Tensor) and v.shape[:1] == (B,)]
+                parts = []
+                for t in range(T):
+                    rows = slice(t * n_streams, (t + 1) * n_streams)
+                    parts.append(trk.step_modes({k: dec[k][rows] for k in keys}, 1))
+                    hist.push(parts[-1]['track_status'])
+                out = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+            else:
+                out = trk.step(dec, T, history=hist)
+            sm = hist.smooth(out)
+            out = dict(out, ori=sm['ori'], pos=sm['pos'], smooth_status=sm['smooth_status'])
         if targets is not None and scorer is not None:
             if scorer.n_groups != n_streams or scorer.n_tracks < 2:
                 raise AssertionError(f'the scorer needs {n_streams} groups and 2 tracks')
@@ -314,7 +349,8 @@ class SPEMi355x:
             scorer.step(1, dict(out, status=out['track_status'] & 8), tg, B // n_streams)
         end.record()
         end.synchronize()
-        tracked = {k: out[k].cpu().numpy() for k in ('ori', 'pos', 'mahalanobis', 'track_status')}
+        tracked = {k: out[k].cpu().numpy() for k in ('ori', 'pos', 'mahalanobis', 'track_status') +
+                   (('smooth_status',) if smooth else ())}
         still = self._pose(dec, check=False)
         if modes:
             tracked['chosen'] = out['chosen'].cpu().numpy()
