@@ -529,6 +529,54 @@ int spef_consensus_keypoints_f64(spef_ctx* ctx, const float* kp, const float* we
 int spef_preprocess(spef_ctx* ctx, const uint8_t* frames, int B, int Hin, int Win, uint8_t* out, int H, int W,
                     void* stream);
 
+/* Track-guided region of interest for keypoint mode (opt-in; nothing calls it unless asked): where the tracker expects
+ * the target, the network sees only that part of the frame, cropped and resized to its input, and the keypoints it
+ * gives are mapped back to the full frame exactly (an affine map), so that spef_decode_keypoints(apply_sigmoid = 0),
+ * spef_consensus_keypoints and spef_refine_keypoints take them unchanged (ROI path;
+ * spef_amd/spe/roi.py is the NumPy twin of the prediction, the box rule and the un-mapping and states every step).
+ * Keypoint mode only: a crop under a soft-classification head changes the apparent attitude.
+ *
+ * spef_track_predict: the one-frame-ahead pose of streams [first_stream, first_stream + n) from the tracker's state,
+ *   which it does not change: quat_out [n x 4] = normalise(exp([w]x) q) in the hemisphere of q, pos_out [n x 3] =
+ *   t + v (fp64, rounded to float32; the conventions of spef_track_step), have_out [n] = 1 where the stream has a
+ *   track, else 0 with a zero pose. SPEF_ERR_ARG for a null pointer or a stream index out of range.
+ * spef_roi_boxes: the box of B poses in frames Hin x Win for a network input H x W, in fp64 without fused
+ *   multiply-adds: project the origin and the n model points of spef_set_keypoints with K (quat2dcm of the quaternion
+ *   as given, spe/utils.py:10-53) and, when spef_set_keypoint_distortion is on, the forward distortion of
+ *   KeyPoints.project (keypoints_utils.py:77-82); take min and max over the n + 1 points
+ *   (create_bbox_from_keypoints, :176-198); grow each side by margin (a fraction of the side) on both ends; raise
+ *   each side to min_side; widen or heighten about the centre to the aspect W / H; round: w = floor(w + 0.5),
+ *   x0 = floor(cx - w / 2 + 0.5), x1 = x0 + w, likewise in y; shift the box into the frame without changing its size.
+ *   have (or NULL) [B]: spef_track_predict's flag.
+ *   box_out [B x 4] int32 (x0, y0, x1, y1), x1 / y1 exclusive; status [B]: bit 1 = the row got the full frame
+ *   (0, 0, Win, Hin): have is 0, the pose is not finite, a point has Z <= 0, a pixel is not finite, or the grown box
+ *   is wider than Win or taller than Hin. SPEF_ERR_ARG: a null required pointer, a size below 1, margin negative or
+ *   not finite, min_side below 1 or not finite; SPEF_ERR_STATE without spef_set_keypoints.
+ * spef_preprocess_roi: spef_preprocess with one box per frame: frames uint8 [B x Hin x Win x 3], box [B x 4] (device,
+ *   as spef_roi_boxes writes it) -> out uint8 [B x H x W x 3], bit-identical to Pillow's
+ *   Image.crop(box).resize((W, H), BILINEAR) -- crop, then resize: no pixel outside the box is read, unlike
+ *   resize(..., box=box). The coefficient tables are computed on the device per frame and axis (Pillow's
+ *   precompute_coeffs, fp64) into tables the context owns; one fused kernel then runs both passes on tiles of the
+ *   output through an 8-bit LDS tile, with Pillow's rounding between them and no temporary in device memory.
+ *   status (or NULL) [B]: 0, or bit 2 for a box that is not inside the frame or has a side below 1 (a caller's own:
+ *   spef_roi_boxes makes none); such a frame is written as zeros and nothing outside the frames is read. B <= 65535.
+ *   The tables grow with B as spef_preprocess' temporary does; a call at a shape seen before allocates nothing.
+ * spef_roi_unmap_keypoints: raw [B x 2(n+1)] head output of the crops -> kp_out (same shape), the normalised
+ *   full-frame keypoints: the sigmoid exactly as spef_decode_keypoints applies it (float32; skipped when apply_sigmoid
+ *   is 0), then u = (x0 + s_u (x1 - x0)) / nu, v = (y0 + s_v (y1 - y0)) / nv in fp64, rounded once to float32.
+ *   SPEF_ERR_STATE without spef_set_keypoints.
+ * All four only enqueue on `stream`: no host synchronisation, and they can be stream-captured once the tables exist. */
+#define SPEF_ROI_FULL_FRAME 1   /* spef_roi_boxes' status: the row fell back to the full frame */
+#define SPEF_ROI_BAD_BOX 2      /* spef_preprocess_roi's status: box not inside the frame, frame written as zeros */
+int spef_track_predict(spef_track* track, int first_stream, int n, float* quat_out, float* pos_out, int* have_out,
+                       void* stream_hip);
+int spef_roi_boxes(spef_ctx* ctx, const float* quat, const float* pos, const int* have, int B, int Hin, int Win, int H,
+                   int W, double margin, double min_side, int* box_out, int* status, void* stream);
+int spef_preprocess_roi(spef_ctx* ctx, const uint8_t* frames, const int* box, int B, int Hin, int Win, uint8_t* out,
+                        int H, int W, int* status, void* stream);
+int spef_roi_unmap_keypoints(spef_ctx* ctx, const float* raw, const int* box, int B, int apply_sigmoid, float* kp_out,
+                             void* stream);
+
 /* Schedule options (both choices of each are bit-identical; the parity tests switch them):
  * SPEF_OPT_FUSE_BLOCKS (default 1): each inverted-residual block as one fused kernel (expand + depthwise + project
  *   on-chip); 0 = one kernel per conv (the reference's module-by-module schedule).

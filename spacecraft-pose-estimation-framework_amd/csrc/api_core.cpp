@@ -135,6 +135,9 @@ int spef_destroy(spef_ctx* c) {
   if (c->pre_bh) hipFree(c->pre_bh);
   if (c->pre_bv) hipFree(c->pre_bv);
   if (c->pre_tmp) hipFree(c->pre_tmp);
+  if (c->roi_tab_h) hipFree(c->roi_tab_h);
+  if (c->roi_tab_v) hipFree(c->roi_tab_v);
+  if (c->roi_valid) hipFree(c->roi_valid);
   if (c->q8_fc_sc) hipFree(c->q8_fc_sc);
   for (hipEvent_t e : c->pool) hipEventDestroy(e);
   delete c;

@@ -336,14 +336,6 @@ int spef_score_log(spef_score* sc, int track, int group, int first, int n, float
 // ------------------------------------------------------------------------------------------ pose tracking
 static_assert(SPEF_TRACK_STATE_DOUBLES == TRACK_STATE, "SPEF_TRACK_STATE_DOUBLES and spef::TRACK_STATE must agree");
 
-struct spef_track {
-  spef_ctx* ctx = nullptr;   // profiler of the step launches
-  int device = 0;
-  int S = 0;
-  TrackParams prm{};
-  double* state = nullptr;   // [S][TRACK_STATE]
-};
-
 int spef_track_destroy(spef_track* tr) {
   if (!tr) return SPEF_OK;
   Dev d(tr->device);   // not through ctx: the context may be gone already

@@ -81,6 +81,14 @@ struct spef_ctx {
   int pre_ksh = 0, pre_ksv = 0, pre_y0 = 0, pre_ht = 0;
   uint8_t* pre_tmp = nullptr;
   size_t pre_tmp_bytes = 0;
+  // region-of-interest preprocessing (spef_preprocess_roi): per-frame coefficient tables for the last (Hin, Win, H, W),
+  // grown with the batch; tile shape and the most source rows a tile can need (api_roi.cpp)
+  int roi_key[4] = {0, 0, 0, 0};
+  int roi_B = 0;
+  int* roi_tab_h = nullptr;   // [B][W (2 + roi_kstr_h)]
+  int* roi_tab_v = nullptr;   // [B][H (2 + roi_kstr_v)]
+  int* roi_valid = nullptr;   // [B]
+  int roi_kstr_h = 0, roi_kstr_v = 0, roi_th = 0, roi_tw = 0, roi_rows_cap = 0;
   std::vector<std::array<int64_t, 3>> q8_res;  // per op: residual-join rescale (R, RB, RS)
   // per-launch HIP-event profiling (bench.py roofline leg)
   bool profiling = false;
@@ -103,6 +111,15 @@ struct spef_observer {
   std::vector<std::array<uint32_t, 7>> geom;   // the op list the taps were laid out for
   uint64_t* state = nullptr;
   uint64_t* tap(int t) const { return state + (size_t)t * (OBS_COUNTERS + OBS_BINS); }
+};
+
+// Pose tracker (api_handles.cpp; api_roi.cpp reads its state for spef_track_predict).
+struct spef_track {
+  spef_ctx* ctx = nullptr;   // profiler of the step launches
+  int device = 0;
+  int S = 0;
+  TrackParams prm{};
+  double* state = nullptr;   // [S][TRACK_STATE]
 };
 
 // A blob parsed and copied into fresh device storage, not yet owned by any context (the first half of a

@@ -390,4 +390,29 @@ hipError_t launch_resize_h(const uint8_t* in, uint8_t* tmp, const int* bounds, c
 hipError_t launch_resize_v(const uint8_t* tmp, uint8_t* out, const int* bounds, const int* kk, int ksize, int B,
                            int Ht, int Ho, int Wo, hipStream_t s);
 
+// ---- track-guided region of interest, keypoint mode (k_roi.hip; spef_amd/spe/roi.py states the arithmetic) ----
+enum : int { ROI_FULL_FRAME = 1, ROI_BAD_BOX = 2 };
+// The tracker's one-frame-ahead pose of n streams from their state rows (read only): quat_out [n][4], pos_out [n][3],
+// have_out [n] (0: no track, the pose is zeros).
+hipError_t launch_track_predict(const double* state, int n, float* quat_out, float* pos_out, int* have_out,
+                                hipStream_t s);
+// The box of B poses (have: null or [B]) for frames Hin x Win and a network input H x W: box_out [B][4] = (x0, y0, x1,
+// y1), x1 / y1 exclusive; status [B] = ROI_FULL_FRAME where the row fell back to (0, 0, Win, Hin).
+hipError_t launch_roi_boxes(const float* quat, const float* pos, const int* have, int B, int n, const float* kp3d,
+                            const double* K, const EpnpDist& dist, int Hin, int Win, int H, int W, double margin,
+                            double min_side, int* box_out, int* status, hipStream_t s);
+// Pillow's coefficient tables per frame for crop(box).resize((W, H), BILINEAR). tab_h [B][W (2 + kstr_h)], tab_v
+// [B][H (2 + kstr_v)]: bounds [out][2] then coefficients [out][kstr]; valid [B]; status (may be null) [B] = ROI_BAD_BOX
+// for a box that is not inside the frame. kstr_h / kstr_v: multiples of 4, at least the full frame's ksize.
+hipError_t launch_roi_coeffs(const int* box, int B, int Hin, int Win, int H, int W, int kstr_h, int kstr_v, int* tab_h,
+                             int* tab_v, int* valid, int* status, hipStream_t s);
+// The fused two-pass resample on tiles of TH x TW output pixels; rows_cap = the most source rows a tile can need.
+size_t roi_resample_lds_bytes(int kstr_h, int kstr_v, int TH, int TW, int rows_cap);
+hipError_t launch_roi_resample(const uint8_t* in, uint8_t* out, const int* tab_h, const int* tab_v, const int* valid,
+                               int B, int Hin, int Win, int H, int W, int kstr_h, int kstr_v, int TH, int TW,
+                               int rows_cap, hipStream_t s);
+// raw [B][nk] head output -> kp_out [B][nk] normalised full-frame keypoints through box [B][4].
+hipError_t launch_roi_unmap(const float* raw, const int* box, int B, int nk, float nu, float nv, int apply_sigmoid,
+                            float* kp_out, hipStream_t s);
+
 }  // namespace spef

@@ -91,6 +91,10 @@ SIGNATURES = {
     'spef_refine_keypoints': (_i, [_vp, _vp, _vp, _i, _i, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'spef_consensus_keypoints': (_i, [_vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'spef_consensus_keypoints_f64': (_i, [_vp, _vp, _vp, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'spef_track_predict': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    'spef_roi_boxes': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
+    'spef_preprocess_roi': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    'spef_roi_unmap_keypoints': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     'spef_profile_begin': (_i, [_vp]),
     'spef_profile_end': (_i, [_vp, C.c_char_p, _sz, C.POINTER(_sz)]),
     'spef_measure_peaks': (_i, [_i, _i, C.POINTER(C.c_double)]),
@@ -119,6 +123,7 @@ class ModesParams(C.Structure):   # spef_modes_params
 
 
 MODES_MAX = 4                          # SPEF_MODES_MAX
+ROI_FULL_FRAME, ROI_BAD_BOX = 1, 2     # spef_roi_boxes' / spef_preprocess_roi's status bits
 
 
 class SpefError(RuntimeError):

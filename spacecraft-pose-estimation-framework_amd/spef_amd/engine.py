@@ -312,6 +312,18 @@ class PoseTracker:
             out['rates'] = ro
         return out
 
+    def predict(self, first: int = 0, n: Optional[int] = None) -> dict:
+        """The one-frame-ahead pose of streams [first, first + n) (``spe.roi.predict``): {'ori' [n x 4], 'pos' [n x 3]
+        float32: q+ = exp([w]x) q, t+ = t + v; 'have' [n] int32: 0 where the stream has no track (zero pose)}. The
+        state is only read; one kernel on the current stream, no host sync."""
+        n = self.n_streams - first if n is None else int(n)
+        dev = self.device
+        qo = torch.empty((max(n, 0), 4), dtype=torch.float32, device=dev)
+        po = torch.empty((max(n, 0), 3), dtype=torch.float32, device=dev)
+        hv = torch.empty((max(n, 0),), dtype=torch.int32, device=dev)
+        L.check(self.lib.spef_track_predict(self.handle, int(first), n, _ptr(qo), _ptr(po), _ptr(hv), _stream(dev)))
+        return {'ori': qo, 'pos': po, 'have': hv}
+
     def reset(self, stream: Optional[int] = None) -> None:
         """Forget one stream's track (all streams: None); enqueued on the current stream."""
         L.check(self.lib.spef_track_reset(self.handle, -1 if stream is None else int(stream), _stream(self.device)))
@@ -602,6 +614,59 @@ class Engine:
             out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=self.device)
         L.check(self.lib.spef_preprocess(self.ctx, _ptr(frames), B, Hin, Win, _ptr(out), H, W, _stream(self.device)))
         return out
+
+    def roi_boxes(self, quat: torch.Tensor, pos: torch.Tensor, frame_size, size, margin: float = 0.2,
+                  min_side: float = 32.0, have: Optional[torch.Tensor] = None):
+        """The box of each pose (``spe.roi.box_of_pose`` states the rule) in frames ``frame_size`` = (Hin, Win) for a
+        network input ``size`` = (H, W): -> (box [B x 4] int32 (x0, y0, x1, y1), x1 / y1 exclusive; status [B] int32,
+        bit 1 = the row got the full frame). ``have`` [B] int32: ``PoseTracker.predict``'s flag. Needs
+        ``set_keypoints``. One kernel on the current stream."""
+        dev = self.device
+        B = quat.shape[0]
+        assert quat.shape == (B, 4) and pos.shape == (B, 3)
+        for t in (quat, pos):
+            assert t.device == dev and t.is_contiguous() and t.dtype == torch.float32
+        if have is not None:
+            assert have.device == dev and have.dtype == torch.int32 and have.numel() == B and have.is_contiguous()
+        box = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        L.check(self.lib.spef_roi_boxes(self.ctx, _ptr(quat), _ptr(pos), _ptr(have), B, int(frame_size[0]),
+                                        int(frame_size[1]), int(size[0]), int(size[1]), float(margin), float(min_side),
+                                        _ptr(box), _ptr(status), _stream(dev)))
+        return box, status
+
+    def preprocess_roi(self, frames: torch.Tensor, boxes: torch.Tensor, size, out: Optional[torch.Tensor] = None,
+                       status: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``preprocess`` with one box per frame: frames uint8 [B, Hin, Win, 3], ``boxes`` int32 [B, 4] (device) ->
+        uint8 [B, H, W, 3] = Pillow ``crop(box).resize((W, H), BILINEAR)``, bit for bit. ``status`` [B] int32, when
+        given, receives 0 or bit 2 (the box is not inside the frame: that frame is zeros)."""
+        dev = self.device
+        assert frames.device == dev and frames.dtype == torch.uint8 and frames.is_contiguous()
+        assert frames.dim() == 4 and frames.shape[3] == 3, 'frames must be B x H x W x 3 uint8'
+        B, Hin, Win, _ = frames.shape
+        assert boxes.device == dev and boxes.dtype == torch.int32 and boxes.is_contiguous() and boxes.shape == (B, 4)
+        if status is not None:
+            assert status.device == dev and status.dtype == torch.int32 and status.numel() == B and status.is_contiguous()
+        H, W = int(size[0]), int(size[1])
+        if out is None:
+            out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        L.check(self.lib.spef_preprocess_roi(self.ctx, _ptr(frames), _ptr(boxes), B, Hin, Win, _ptr(out), H, W,
+                                             _ptr(status), _stream(dev)))
+        return out
+
+    def unmap_keypoints(self, raw: torch.Tensor, boxes: torch.Tensor, apply_sigmoid: bool = True) -> torch.Tensor:
+        """Raw head output of crops [B x 2(n+1)] -> the normalised full-frame keypoints (``spe.roi.unmap``): what
+        ``decode_keypoints(apply_sigmoid=False)``, ``consensus_keypoints`` and ``refine_keypoints`` take."""
+        dev = self.device
+        B = raw.shape[0]
+        assert raw.device == dev and raw.dtype == torch.float32 and raw.is_contiguous() and raw.dim() == 2
+        assert boxes.device == dev and boxes.dtype == torch.int32 and boxes.is_contiguous() and boxes.shape == (B, 4)
+        cfg = getattr(self, '_kp', None)   # without set_keypoints the library refuses (SPEF_ERR_STATE)
+        assert cfg is None or raw.shape[1] == 2 * (cfg[0].shape[0] + 1), 'raw must be B x 2(n+1)'
+        kp = torch.empty_like(raw)
+        L.check(self.lib.spef_roi_unmap_keypoints(self.ctx, _ptr(raw), _ptr(boxes), B, 1 if apply_sigmoid else 0,
+                                                  _ptr(kp), _stream(dev)))
+        return kp
 
     def backbone(self, x: torch.Tensor) -> torch.Tensor:
         layout, B, H, W = self._layout(x)

@@ -26,6 +26,12 @@ pose of any head, keypoint mode included, with the device tracker (csrc/k_track.
 ``video_type='Smoother'`` (``predict_sequence`` only: a recorded video) is the tracker followed by a fixed-interval
 smoother over the T frames of the call (csrc/k_smooth.hip, ``PoseHistory.smooth``): ``pose_video`` is the smoothed pose
 and also has 'smooth_status'. ``predict`` raises ValueError for it: a single frame has nothing to smooth.
+
+``video_type='TrackerROI'`` (``predict_sequence`` only, keypoint mode only) is the tracker on raw camera frames, uint8
+[T, Hin, Win, 3], with a track-guided region of interest (``SPEMi355x.predict_tracked_roi``): each frame is cropped to
+the box of the pose the tracker predicts for it and resized to ``Inference.roi_size`` = (H, W), the network input, and
+the keypoints are mapped back to the full frame before EPnP. ``Inference.roi_params``: margin, min_side. Both poses
+also hold 'roi' (x0, y0, x1, y1) and 'roi_status'.
 """
 from __future__ import annotations
 
@@ -70,6 +76,8 @@ class Inference:
         self.tracker_params = {}     # video_type 'Tracker': the parameters of Engine.tracker (q, p0, r, gate_chi2, ...)
         self.tracker_pdf_cov = False  # video_type 'Tracker': SPEMi355x.predict_tracked(pdf_cov=True), the PDFs' covariance
         self.tracker_modes = 0       # video_type 'Tracker': predict_tracked(modes=K), up to K orientation hypotheses per frame
+        self.roi_size = None         # video_type 'TrackerROI': the network input (H, W) the crops are resized to
+        self.roi_params = {}         # video_type 'TrackerROI': margin, min_side of SPEMi355x.predict_tracked_roi
         self.img_size = None
         self.device = device
         self.dtype = dtype
@@ -150,13 +158,14 @@ class Inference:
                 self.prev_still_ori = ori[t]
         return ori
 
-    def _tracked(self, images: torch.Tensor, smooth: bool = False) -> list:
+    def _tracked(self, images: torch.Tensor, smooth: bool = False, roi: bool = False) -> list:
         """video_type 'Tracker' for T consecutive frames of one video: one batched forward, one decode and one
         tracker step on the GPU (``SPEMi355x.predict_tracked``, one stream; the state stays in the device tracker, so
         any cut of a video into calls gives the same poses). -> T triples (pose_still, latency_ms, pose_video) with
         pose_video = {'ori', 'pos', 'mahalanobis', 'track_status', 'keypoints', 'bbox'}; in keypoint mode its
         'keypoints' are the reprojection of the tracked pose. With ``smooth`` (video_type 'Smoother') the pose is the
-        fixed-interval smoother's over these T frames and pose_video also has 'smooth_status'."""
+        fixed-interval smoother's over these T frames and pose_video also has 'smooth_status'. With ``roi`` (video_type
+        'TrackerROI') ``images`` are raw uint8 frames [T, Hin, Win, 3] and the loop is ``predict_tracked_roi``'s."""
         eng, su = self.inference_engine, self.spe_utils
         if not hasattr(eng, 'predict_tracked'):
             raise ValueError("video filtering 'Tracker' needs the 'gpu_mi355x' engine")
@@ -164,8 +173,14 @@ class Inference:
         pdf_cov = {'pdf_cov': True} if self.tracker_pdf_cov else {}
         modes = {'modes': int(self.tracker_modes)} if self.tracker_modes else {}
         smoothing = {'smooth': True} if smooth else {}
-        still, tracked, latency_ms = eng.predict_tracked(images, 1, **pdf_cov, **modes, **smoothing,
-                                                         **self.tracker_params)
+        if roi:
+            if self.roi_size is None:
+                raise ValueError("video filtering 'TrackerROI' needs Inference.roi_size = (H, W), the network input")
+            still, tracked, latency_ms = eng.predict_tracked_roi(images, self.roi_size, 1, **self.roi_params,
+                                                                 **self.tracker_params)
+        else:
+            still, tracked, latency_ms = eng.predict_tracked(images, 1, **pdf_cov, **modes, **smoothing,
+                                                             **self.tracker_params)
         still = dict(still)
         still['ori'] = self._still_pole(still['ori'])
         found = still.pop('modes', None)     # tracker_modes: a dict of per-frame arrays
@@ -199,6 +214,10 @@ class Inference:
         step and read back after it, so ``reset()`` clears both and the two calls can be mixed on one video.
         An engine without ``predict_video`` (one of the reference's own, through ``engine_factories``) is driven
         frame by frame."""
+        if video_type == 'TrackerROI':              # raw frames; the tracker decides what the network sees
+            if self.roi_size is not None:
+                self.img_size = (1, 3) + tuple(int(v) for v in self.roi_size)
+            return self._tracked(images, roi=True)
         if video_type in ('Tracker', 'Smoother'):   # 'Smoother': the tracker and a backward pass over these T frames
             self.img_size = (1,) + tuple(images.size())[1:]
             return self._tracked(images, smooth=video_type == 'Smoother')

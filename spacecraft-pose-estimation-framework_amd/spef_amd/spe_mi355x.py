@@ -358,6 +358,62 @@ class SPEMi355x:
                               'n': dec['n_modes'].cpu().numpy(), 'chosen': tracked['chosen']}
         return still, tracked, start.elapsed_time(end)
 
+    def predict_tracked_roi(self, frames: torch.Tensor, img_size, n_streams: int = 1, margin: float = 0.2,
+                            min_side: float = 32.0, **params) -> Tuple[Dict, Dict, float]:
+        """``predict_tracked`` on raw camera frames with a track-guided region of interest, keypoint mode only
+        (ValueError otherwise): ``frames`` uint8 [T * n_streams, Hin, Win, 3], time-major. The network sees, per frame,
+        the box of the pose the tracker predicts for it (``Engine.roi_boxes``: the projected model grown by ``margin``,
+        at least ``min_side`` px, at the aspect of ``img_size``) cropped and resized to ``img_size`` = (H, W); the
+        keypoints it gives are mapped back to the full frame before EPnP, so the head's error costs box width / nu as
+        many pixels. The first frame of a stream, and every frame while it has no track, gets the full frame through
+        the same kernels. Time is sequential by nature: per step predict -> boxes -> crop-resize of the step's
+        ``n_streams`` frames -> forward -> un-map -> ``decode_keypoints(apply_sigmoid=False)`` with the configured
+        consensus and refinement -> ``tracker.step(T=1)``, all enqueued on one stream with no host synchronisation
+        inside the loop. -> (still pose, tracked pose, latency ms) as ``predict_tracked``; both dicts also hold 'roi'
+        [T * n_streams x 4] int32 (x0, y0, x1, y1) and 'roi_status' (bit 1: full frame). The model must have been
+        trained on such crops; training is not this project's. ``params``: as
+        ``Engine.tracker``."""
+        if self.engine is None:
+            raise AssertionError('no model loaded')
+        if not self.keypoint_mode:
+            raise ValueError('predict_tracked_roi needs keypoint mode: a crop under a soft-classification head '
+                             'changes the apparent attitude')
+        x = frames.to(self.device, non_blocking=True).contiguous()
+        if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+            raise AssertionError('frames must be raw uint8 [T * n_streams, Hin, Win, 3]')
+        B, S = x.shape[0], int(n_streams)
+        if S < 1 or B % S:
+            raise AssertionError(f'{B} frames are not whole time steps of {S} streams')
+        T, eng = B // S, self.engine
+        frame_size, size = (x.shape[1], x.shape[2]), (int(img_size[0]), int(img_size[1]))
+        want_cov = self.keypoint_refine is not None or self.keypoint_consensus is not None
+        trk = self.tracker(S, **params)
+        torch.cuda.synchronize(self.device)
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        decs, outs, rois, stats = [], [], [], []
+        for t in range(T):
+            pred = trk.predict()
+            box, bst = eng.roi_boxes(pred['ori'], pred['pos'], frame_size, size, margin, min_side, have=pred['have'])
+            small = eng.preprocess_roi(x[t * S:(t + 1) * S], box, size)
+            raw0, _ = eng.forward(small)
+            kp = eng.unmap_keypoints(raw0, box, apply_sigmoid=True)
+            dec = eng.decode_keypoints(kp, apply_sigmoid=False, want_cov=want_cov)
+            outs.append(trk.step(dec, 1))
+            decs.append(dec)
+            rois.append(box)
+            stats.append(bst)
+        end.record()
+        end.synchronize()
+        dec = {k: torch.cat([d[k] for d in decs]) for k in decs[0]}
+        out = {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
+        roi, roi_status = torch.cat(rois).cpu().numpy(), torch.cat(stats).cpu().numpy()
+        tracked = {k: out[k].cpu().numpy() for k in ('ori', 'pos', 'mahalanobis', 'track_status')}
+        still = self._pose(dec, check=False)
+        for d in (still, tracked):
+            d['roi'], d['roi_status'] = roi, roi_status
+        return still, tracked, start.elapsed_time(end)
+
     def _pose(self, dec, check: bool = True, want_cov: bool = False) -> Dict:
         status = dec['status'].cpu().numpy() if check else np.zeros(1, np.int32)
         if np.any(status & 1):
