@@ -577,6 +577,97 @@ int spef_preprocess_roi(spef_ctx* ctx, const uint8_t* frames, const int* box, in
 int spef_roi_unmap_keypoints(spef_ctx* ctx, const float* raw, const int* box, int B, int apply_sigmoid, float* kp_out,
                              void* stream);
 
+/* Head fit (opt-in; nothing calls it unless asked): fit the URSONet head's two Linear layers (ursonet.py:17-25) on the
+ * device over cached backbone features, the backbone frozen (Head-fit path;
+ * spef_amd/solver/head_fit.py is the NumPy twin and states every step, the hash and the order of every float32
+ * operation). It stands where the reference's train.py + SPELoss (src/solver/loss.py) + import_optimizer
+ * (src/solver/optimizer.py) stand when only the head is trained.
+ *
+ * spef_features: the backbone through the global mean; pooled_out receives fp32 [B x feat_c] (1280), the values
+ *   spef_forward hands to its FC at the same schedule, bit for bit. Needs spef_reserve as spef_forward does. URSONet-head
+ *   blobs only (SPEF_ERR_STATE for a keypoint blob, and for an int8 blob, whose pooled buffer holds codes).
+ *
+ * spef_encode_targets: OrientationSoftClassification.encode (classification_utils.py:85-111) and
+ *   PositionSoftClassification.encode (:217-240) of B poses on the context's decode tables: quat [B x 4] / pos [B x 3]
+ *   (device, fp64: a float32 quaternion moves a target by more than the reference's own encode is pinned to) ->
+ *   ori_soft [B x n_ori bins] / pos_soft [B x n_pos bins] float32; either pair may be NULL. params: the two variances,
+ *   (smooth / n_bins_per_dim)^2 / 12 per head, computed by the caller (both > 0 and finite). mask (NULL, or device uint8
+ *   [n_ori bins]): the reference's redundant_flags; a masked bin gets kernel 0, the delete_unused_bins = False case.
+ *   fp64 without fused multiply-adds, the normalising sum in a fixed order, rounded once to float32. enc_status
+ *   [B x 2] (orientation, position; a word of its own): 1 = a non-finite input or a kernel sum that is zero or not finite
+ *   (the reference raises there); that row of that head is NaN, its neighbours are untouched. SPEF_ERR_STATE when a table
+ *   that is needed is not set. One launch, one workgroup per (row, head); no atomics, no allocation, no host
+ *   synchronisation.
+ *
+ * spef_headfit_create: a trainer for K features (K % 16 == 0) and n_ori + n_pos outputs, independent of the loaded
+ *   model's sizes; the context is used for its device and must outlive the trainer. It owns W [Np x K] (Np = n_ori + n_pos
+ *   rounded up to 16, rows = ori then pos: the layout of the blob's FC op), bias [Np], two optimizer state tensors of
+ *   each shape (SGD: the momentum buffer; Adam: exp_avg, exp_avg_sq), G [Bmax x Np], the dropout copy of X, the logits
+ *   and a step counter, all on the device, all zero at first. The only call here that allocates or synchronises.
+ *   spef_headfit_params:
+ *     ori_mode  SPEF_CLASSIFICATION (SPEF_REGRESSION: SPEF_ERR_ARG, out of scope). pos_mode SPEF_CLASSIFICATION, or
+ *               SPEF_REGRESSION with n_pos == 3.
+ *     optimizer SPEF_HEADFIT_SGD (torch.optim.SGD with momentum, dampening 0) or SPEF_HEADFIT_ADAM (torch.optim.Adam),
+ *               both with L2 weight decay added to the gradient: what import_optimizer builds.
+ *     beta, norm_distance  SPELoss' (loss.py:125). momentum; beta1, beta2, eps (Adam); weight_decay >= 0.
+ *     dropout_p in [0, 1): nn.Dropout on the orientation branch's input (the reference's 0.2; 0 = off); seed.
+ *     Bmax >= 1: the largest batch of a step.
+ * spef_headfit_step: one optimisation step on X [B x K] (1 <= B <= Bmax), ori_target [B x n_ori] soft labels,
+ *   pos_target [B x n_pos] soft labels or [B x 3] positions. With train = 0 it is an evaluation: loss only, no dropout,
+ *   neither the weights nor the state nor the counter change (grad_out must be NULL).
+ *   Loss: orientation and position classification -mean_b sum_i t log softmax(z) (SoftClassLoss, loss.py:109, on
+ *   SPEUtils.last_activ's softmax), log p computed as z - max - log(sum) so that a zero probability under a zero target
+ *   adds 0; position regression PosRegLoss as written (loss.py:35-37): the Frobenius norm of pred - target over the whole
+ *   batch, divided by the target's with norm_distance; total = beta * ori + pos (loss.py:157).
+ *   loss_out (or NULL): device float[3] = total, orientation, position. logits_out (or NULL) [B x (n_ori + n_pos)].
+ *   grad_out (or NULL) [Np x K] then [Np]: dLoss/dW and dLoss/dbias before weight decay (validation and inspection; the
+ *   step itself never writes dW to memory).
+ *   lr is a DEVICE pointer to one float, read by the update kernel when it runs, and the step counter (the dropout
+ *   hash's step, Adam's bias corrections) is read and advanced on the device: a captured step replays correctly, each
+ *   replay one step further, at whatever the caller has written to *lr meanwhile.
+ *   No allocation, no host synchronisation and no atomics; every sum has a fixed order, so a step is deterministic.
+ * spef_headfit_set_weights / _get_weights: copy W [(n_ori + n_pos) x K] and bias [n_ori + n_pos] (no padding) from / to
+ *   device buffers. spef_headfit_get_state: the two state tensors of W and of bias, same shapes (any may be NULL).
+ *   spef_headfit_get_g: G = dLoss/dlogits [B x (n_ori + n_pos)] of the last step or evaluation of B rows (1 <= B <= Bmax;
+ *   validation and inspection). spef_headfit_get_raw: one of the trainer's tensors as it lies in memory, padding rows
+ *   included: `which` = SPEF_HEADFIT_RAW_W / _S1 / _S2 [Np x K], _BIAS / _BIAS_S1 / _BIAS_S2 [Np], _XD [Bmax x K] (the
+ *   dropout copy of X the last training step wrote); SPEF_ERR_ARG for a tensor the trainer does not have (S2 under SGD,
+ *   XD with dropout off). spef_headfit_reset_state zeroes the state and the step counter. All enqueued on `stream`.
+ * spef_headfit_load_model / spef_headfit_commit: copy the head from / to the context's FC op, device to device,
+ *   enqueued. SPEF_ERR_STATE without a loaded fp32-head URSONet blob (int8 blobs hold an int8 head), SPEF_ERR_ARG unless
+ *   K, n_ori and n_pos equal the blob's. After a commit spef_forward uses the new head. */
+enum spef_headfit_optimizer { SPEF_HEADFIT_SGD = 0, SPEF_HEADFIT_ADAM = 1 };
+enum spef_headfit_raw {
+  SPEF_HEADFIT_RAW_W = 0, SPEF_HEADFIT_RAW_BIAS, SPEF_HEADFIT_RAW_S1, SPEF_HEADFIT_RAW_BIAS_S1, SPEF_HEADFIT_RAW_S2,
+  SPEF_HEADFIT_RAW_BIAS_S2, SPEF_HEADFIT_RAW_XD
+};
+typedef struct {
+  int ori_mode, pos_mode, optimizer, norm_distance, Bmax;
+  uint32_t seed;
+  double beta, momentum, beta1, beta2, eps, weight_decay, dropout_p;
+} spef_headfit_params;
+typedef struct spef_headfit spef_headfit;
+typedef struct { double ori_var, pos_var; } spef_encode_params;
+int spef_features(spef_ctx* ctx, const void* input, int layout, int B, int H, int W, float* pooled_out, void* stream);
+/* The width of a spef_features row (the blob's feat_c, 1280 for MobileNetV2); SPEF_ERR_STATE without weights. */
+int spef_feature_width(const spef_ctx* ctx, int* feat_c);
+int spef_encode_targets(spef_ctx* ctx, const double* quat, const double* pos, int B, const spef_encode_params* params,
+                        const uint8_t* mask, float* ori_soft, float* pos_soft, int* enc_status, void* stream);
+int spef_headfit_create(spef_ctx* ctx, int K, int n_ori, int n_pos, const spef_headfit_params* params,
+                        spef_headfit** out);
+int spef_headfit_step(spef_headfit* trainer, const float* X, const float* ori_target, const float* pos_target, int B,
+                      const float* lr, int train, float* loss_out, float* logits_out, float* grad_out, void* stream);
+int spef_headfit_set_weights(spef_headfit* trainer, const float* W, const float* bias, void* stream);
+int spef_headfit_get_weights(spef_headfit* trainer, float* W, float* bias, void* stream);
+int spef_headfit_get_state(spef_headfit* trainer, float* W_s1, float* bias_s1, float* W_s2, float* bias_s2,
+                           void* stream);
+int spef_headfit_get_g(spef_headfit* trainer, int B, float* G, void* stream);
+int spef_headfit_get_raw(spef_headfit* trainer, int which, float* out, void* stream);
+int spef_headfit_reset_state(spef_headfit* trainer, void* stream);
+int spef_headfit_load_model(spef_headfit* trainer, spef_ctx* ctx, void* stream);
+int spef_headfit_commit(spef_headfit* trainer, spef_ctx* ctx, void* stream);
+int spef_headfit_destroy(spef_headfit* trainer);
+
 /* Schedule options (both choices of each are bit-identical; the parity tests switch them):
  * SPEF_OPT_FUSE_BLOCKS (default 1): each inverted-residual block as one fused kernel (expand + depthwise + project
  *   on-chip); 0 = one kernel per conv (the reference's module-by-module schedule).

@@ -688,6 +688,28 @@ int spef_backbone(spef_ctx* c, const void* input, int layout, int B, int H, int 
   return run_backbone(c, input, layout, B, H, W, s, 2, -1, nullptr, features);
 }
 
+int spef_feature_width(const spef_ctx* c, int* feat_c) {
+  if (!c || !feat_c) return fail(SPEF_ERR_ARG, "null argument");
+  if (!c->loaded) return fail(SPEF_ERR_STATE, "weights not loaded (spef_load_weights)");
+  *feat_c = (int)c->hdr.feat_c;
+  return SPEF_OK;
+}
+
+int spef_features(spef_ctx* c, const void* input, int layout, int B, int H, int W, float* pooled_out, void* stream) {
+  int rc = check_ready(c, B, H, W);
+  if (rc) return rc;
+  if (!input || !pooled_out) return fail(SPEF_ERR_ARG, "null input/output");
+  if (layout != SPEF_IN_U8_NHWC && layout != SPEF_IN_F32_NCHW) return fail(SPEF_ERR_ARG, "bad layout");
+  if (c->hdr.head != HEAD_URSONET) return fail(SPEF_ERR_STATE, "spef_features needs a URSONet-head blob");
+  if (c->hdr.dtype == DT_I8) return fail(SPEF_ERR_STATE, "spef_features: an int8 blob's pooled buffer holds codes");
+  Dev d(c->device);
+  hipStream_t s = (hipStream_t)stream;
+  rc = run_backbone(c, input, layout, B, H, W, s, 0, -1, nullptr);   // exactly spef_forward's run up to its FC
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(pooled_out, c->pooled, (size_t)B * c->hdr.feat_c * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return SPEF_OK;
+}
+
 int spef_probe(spef_ctx* c, const void* input, int layout, int B, int H, int W, int stop_op, float* out, int* oc,
                int* oh, int* ow, void* stream) {
   int rc = check_ready(c, B, H, W);

@@ -222,6 +222,42 @@ hipError_t launch_decode_modes(const float* ori_pdf, int n_ori, const double* q_
                                float* mode_quat, float* mode_mass, float* mode_cov, int* n_modes, int* modes_status,
                                hipStream_t s);
 
+// ---- head fit (k_headfit.hip; the arithmetic is stated in spef_amd/solver/head_fit.py) ----
+// The soft-classification targets of B poses (quat [B][4], pos [B][3], fp64) on the decode tables: ori_soft [B][n_ori] /
+// pos_soft [B][n_pos] (either nullable), mask (nullable) [n_ori] = the redundant bins, status [B][2] (ori, pos: 1 = the
+// row is NaN). One workgroup per (row, head).
+hipError_t launch_encode_targets(const double* quat, const double* pos, int B, const double* q_bins, int n_ori,
+                                 const double* grid, int n_pos, double ori_var, double pos_var, const uint8_t* mask,
+                                 float* ori_soft, float* pos_soft, int* status, hipStream_t s);
+enum : int { HF_SGD = 0, HF_ADAM = 1 };   // spef_headfit_optimizer
+struct HeadFitShape {
+  int K, n_ori, n_pos, Np, Bmax;   // Np = n_ori + n_pos rounded up to 16: the row count of W, the row pitch of G
+};
+struct HeadFitOpt {
+  int kind;
+  double momentum, beta1, beta2, eps, weight_decay;
+};
+// Xd = keep ? X * inv_keep : 0 over B * K elements, keep = hash(seed, counter[0], element) >= thr.
+hipError_t launch_headfit_dropout(const float* X, float* Xd, int B, int K, uint32_t seed, uint32_t thr, float inv_keep,
+                                  const uint32_t* counter, hipStream_t s);
+// Row losses (rowloss [2][Bmax] fp64: ori, pos; rowaux [Bmax]: a regression row's sum of target^2) and G [B][Np] of the
+// classification heads from the logits Zo [B][n_ori] / Zp [B][n_pos] and the targets; so / sp = the heads' scale / B.
+// logits_out (nullable) [B][n_ori + n_pos].
+hipError_t launch_headfit_loss(const HeadFitShape& d, const float* Zo, const float* To, const float* Zp, const float* Tp,
+                               int B, int pos_reg, float so, float sp, float* G, double* rowloss, double* rowaux,
+                               float* logits_out, hipStream_t s);
+// Batch means -> loss_out [3] (total, ori, pos; nullable), the regression head's G, and with `train` the step counter
+// (counter[0] steps completed, counter[1] this step's index) and Adam's bias corrections sc [2].
+hipError_t launch_headfit_finish(const HeadFitShape& d, const double* rowloss, const double* rowaux, int B, int pos_reg,
+                                 int norm_distance, double beta, const float* Zp, const float* Tp, float* G, int train,
+                                 double beta1, double beta2, uint32_t* counter, float* sc, float* loss_out,
+                                 hipStream_t s);
+// dW = G^T Xsel (rows below n_ori contract with Xo, the others with Xp) fused with the optimizer step on W [Np][K], bias
+// [Np] and their state (S2 / bS2 unused by SGD); lr: device float; grad_out (nullable) [Np * K + Np].
+hipError_t launch_headfit_update(const HeadFitShape& d, const HeadFitOpt& opt, const float* G, const float* Xo,
+                                 const float* Xp, int B, float* W, float* S1, float* S2, float* bias, float* bS1,
+                                 float* bS2, float* grad_out, const float* lr, const float* sc, hipStream_t s);
+
 // ---- adaptive video filter (k_video.hip; TemporalPDF.update_pdf, src/temporal/pdf_compare.py:94-134) ----
 // Frames are time-major: row t * S + s is time step t of stream s. One head (ori or pos) of the filter:
 struct VideoHead {

@@ -95,6 +95,20 @@ SIGNATURES = {
     'spef_roi_boxes': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
     'spef_preprocess_roi': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     'spef_roi_unmap_keypoints': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    'spef_feature_width': (_i, [_vp, _ip]),
+    'spef_features': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'spef_encode_targets': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'spef_headfit_create': (_i, [_vp, _i, _i, _i, _vp, C.POINTER(_vp)]),
+    'spef_headfit_step': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    'spef_headfit_set_weights': (_i, [_vp, _vp, _vp, _vp]),
+    'spef_headfit_get_weights': (_i, [_vp, _vp, _vp, _vp]),
+    'spef_headfit_get_state': (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    'spef_headfit_get_g': (_i, [_vp, _i, _vp, _vp]),
+    'spef_headfit_get_raw': (_i, [_vp, _i, _vp, _vp]),
+    'spef_headfit_reset_state': (_i, [_vp, _vp]),
+    'spef_headfit_load_model': (_i, [_vp, _vp, _vp]),
+    'spef_headfit_commit': (_i, [_vp, _vp, _vp]),
+    'spef_headfit_destroy': (_i, [_vp]),
     'spef_profile_begin': (_i, [_vp]),
     'spef_profile_end': (_i, [_vp, C.c_char_p, _sz, C.POINTER(_sz)]),
     'spef_measure_peaks': (_i, [_i, _i, C.POINTER(C.c_double)]),
@@ -122,6 +136,19 @@ class ModesParams(C.Structure):   # spef_modes_params
                 ('min_mass', C.c_double), ('floor_var', C.c_double)]
 
 
+class HeadFitParams(C.Structure):   # spef_headfit_params
+    _fields_ = [('ori_mode', C.c_int), ('pos_mode', C.c_int), ('optimizer', C.c_int), ('norm_distance', C.c_int),
+                ('Bmax', C.c_int), ('seed', C.c_uint32), ('beta', C.c_double), ('momentum', C.c_double),
+                ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double), ('weight_decay', C.c_double),
+                ('dropout_p', C.c_double)]
+
+
+class EncodeParams(C.Structure):    # spef_encode_params
+    _fields_ = [('ori_var', C.c_double), ('pos_var', C.c_double)]
+
+
+HEADFIT_RAW = {'W': 0, 'bias': 1, 'W_s1': 2, 'bias_s1': 3, 'W_s2': 4, 'bias_s2': 5, 'Xd': 6}   # spef_headfit_raw
+HEADFIT_SGD, HEADFIT_ADAM = 0, 1      # spef_headfit_optimizer
 MODES_MAX = 4                          # SPEF_MODES_MAX
 ROI_FULL_FRAME, ROI_BAD_BOX = 1, 2     # spef_roi_boxes' / spef_preprocess_roi's status bits
 

@@ -268,6 +268,37 @@ def assemble(dtype_code: int, head: int, n0: int, n1: int, fh: int, fw: int, ops
     return bytes(out)
 
 
+def replace_head(blob_bytes: bytes, w_ori, b_ori, w_pos, b_pos) -> bytes:
+    """A copy of a float URSONet blob with the head's two Linear layers replaced (what ``HeadTrainer.weights`` returns,
+    split at n_out0): the FC op's fp32 tensors are overwritten in place, every other byte is kept. The widths must be the
+    blob's; int8 blobs (an int8 head with its own scales) are refused."""
+    info = describe(blob_bytes)
+    if info['head'] != HEAD_URSONET or info['dtype'] == DT_I8:
+        raise ValueError('replace_head needs a URSONet blob with a float head')
+    fc = [o for o in info['ops'] if o[0] == OP_FC]
+    if len(fc) != 1:
+        raise ValueError('blob has no FC op')
+    K, n, w0, b0 = fc[0][1], fc[0][2], fc[0][8], fc[0][9]
+    n0, n1 = info['n_out0'], info['n_out1']
+    wo, bo = np.asarray(w_ori, np.float32), np.asarray(b_ori, np.float32)
+    wp, bp = np.asarray(w_pos, np.float32), np.asarray(b_pos, np.float32)
+    if wo.shape != (n0, K) or bo.shape != (n0,) or wp.shape != (n1, K) or bp.shape != (n1,) or n != n0 + n1:
+        raise ValueError(f'head shapes {wo.shape} {bo.shape} {wp.shape} {bp.shape} do not match the blob '
+                         f'({n0} + {n1} outputs, {K} features)')
+    np_ = (n + 15) // 16 * 16
+    wf = np.zeros((np_, K), np.float32)
+    wf[:n0], wf[n0:n] = wo, wp
+    bf = np.zeros(np_, np.float32)
+    bf[:n0], bf[n0:n] = bo, bp
+    out = bytearray(blob_bytes)
+    for off, a in ((w0, wf), (b0, bf)):
+        p = info['data_off'] + off
+        if off == ABSENT or p + a.nbytes > len(out):
+            raise ValueError('FC tensor lies outside the blob')
+        out[p:p + a.nbytes] = a.tobytes()
+    return bytes(out)
+
+
 def describe(blob: bytes) -> dict:
     """Parse a blob header + op table (for tests and tooling)."""
     h = _HDR.unpack_from(blob, 0)

@@ -507,6 +507,148 @@ class ActivationObserver:
             pass
 
 
+class HeadTrainer:
+    """Device state of a head fit (``Engine.head_trainer``; csrc/k_headfit.hip, every step is stated in
+    ``spef_amd.solver.head_fit``): the URSONet head's two Linear layers, their optimizer state and a step counter, trained
+    on cached backbone features (``Engine.features``) against soft targets (``Engine.encode_targets``).
+
+    ``step`` and ``evaluate`` only enqueue kernels on the current stream (no allocation in the library, no host sync, no
+    atomics) and can be captured in a HIP graph: the learning rate is read from the device tensor ``self.lr`` when the
+    update kernel runs and the step counter lives on the device, so every replay is one step further at the rate
+    ``set_lr`` last wrote.
+
+    Parameters: ``optimizer`` 'sgd' (torch.optim.SGD with ``momentum``) or 'adam' (torch.optim.Adam with ``beta1``,
+    ``beta2``, ``eps``), both with L2 ``weight_decay``; ``pos_mode`` 'classification' or 'regression'; ``beta`` and
+    ``norm_distance`` of the reference's SPELoss; ``dropout_p`` on the orientation branch's input (0 = off) with ``seed``;
+    ``Bmax`` the largest batch of a step; ``lr`` the initial learning rate."""
+
+    def __init__(self, engine: 'Engine', K: int, n_ori: int, n_pos: int, optimizer: str = 'sgd',
+                 pos_mode: str = 'classification', beta: float = 1.0, norm_distance: bool = False,
+                 momentum: float = 0.9, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                 weight_decay: float = 0.0, dropout_p: float = 0.0, seed: int = 0, Bmax: int = 64, lr: float = 0.01,
+                 ori_mode: str = 'classification'):
+        self.engine = engine
+        self.lib = engine.lib
+        self.device = engine.device
+        self.K, self.n_ori, self.n_pos, self.Bmax = int(K), int(n_ori), int(n_pos), int(Bmax)
+        self.optimizer, self.pos_mode = optimizer, pos_mode
+        modes = {'regression': L.REGRESSION, 'classification': L.CLASSIFICATION}
+        assert optimizer in ('sgd', 'adam'), "optimizer must be 'sgd' or 'adam'"
+        assert ori_mode in modes and pos_mode in modes, 'modes are regression or classification'
+        prm = L.HeadFitParams(modes[ori_mode], modes[pos_mode], L.HEADFIT_ADAM if optimizer == 'adam' else L.HEADFIT_SGD,
+                              int(bool(norm_distance)), self.Bmax, int(seed) & 0xFFFFFFFF, float(beta), float(momentum),
+                              float(beta1), float(beta2), float(eps), float(weight_decay), float(dropout_p))
+        h = C.c_void_p()
+        L.check(self.lib.spef_headfit_create(engine.ctx, self.K, self.n_ori, self.n_pos, C.byref(prm), C.byref(h)))
+        self.handle = h
+        self.lr = torch.full((1,), float(lr), dtype=torch.float32, device=self.device)
+
+    def set_lr(self, lr: float) -> None:
+        """Write the learning rate the next steps (and replays of captured ones) read; enqueued."""
+        self.lr.fill_(float(lr))
+
+    def _check(self, X, ori_target, pos_target):
+        B = X.shape[0]
+        for t, w in ((X, self.K), (ori_target, self.n_ori), (pos_target, self.n_pos)):
+            assert t.device == self.device and t.dtype == torch.float32 and t.is_contiguous()
+            assert tuple(t.shape) == (B, w), f'expected {B} x {w}, got {tuple(t.shape)}'
+        return B
+
+    def step(self, X: torch.Tensor, ori_target: torch.Tensor, pos_target: torch.Tensor, want_logits: bool = False,
+             want_grad: bool = False, loss: Optional[torch.Tensor] = None) -> dict:
+        """One optimisation step on features ``X`` [B x K] with soft targets ``ori_target`` [B x n_ori] and
+        ``pos_target`` ([B x n_pos] soft labels, or [B x 3] positions in regression mode). -> {'loss': device float32 [3]
+        = total, orientation, position (``loss``, when given, is written and returned), 'logits' [B x (n_ori + n_pos)],
+        'grad_w' [Np x K] / 'grad_b' [Np] (dLoss/dW, dLoss/dbias before weight decay; Np = the widths rounded up to 16)}."""
+        return self._run(X, ori_target, pos_target, 1, want_logits, want_grad, loss)
+
+    def evaluate(self, X: torch.Tensor, ori_target: torch.Tensor, pos_target: torch.Tensor, want_logits: bool = False,
+                 loss: Optional[torch.Tensor] = None) -> dict:
+        """The loss (and logits) of a batch without dropout; nothing in the trainer changes."""
+        return self._run(X, ori_target, pos_target, 0, want_logits, False, loss)
+
+    def _run(self, X, ori_target, pos_target, train, want_logits, want_grad, loss):
+        B = self._check(X, ori_target, pos_target)
+        n, Np = self.n_ori + self.n_pos, (self.n_ori + self.n_pos + 15) // 16 * 16
+        out = {'loss': loss if loss is not None else torch.empty(3, dtype=torch.float32, device=self.device)}
+        if want_logits:
+            out['logits'] = torch.empty((B, n), dtype=torch.float32, device=self.device)
+        grad = torch.empty(Np * self.K + Np, dtype=torch.float32, device=self.device) if want_grad else None
+        L.check(self.lib.spef_headfit_step(self.handle, _ptr(X), _ptr(ori_target), _ptr(pos_target), B, _ptr(self.lr),
+                                           train, _ptr(out['loss']), _ptr(out.get('logits')), _ptr(grad),
+                                           _stream(self.device)))
+        if want_grad:
+            out['grad_w'], out['grad_b'] = grad[:Np * self.K].view(Np, self.K), grad[Np * self.K:]
+        return out
+
+    def weights(self):
+        """-> (W [(n_ori + n_pos) x K], bias [n_ori + n_pos]) device copies; rows = orientation then position."""
+        n = self.n_ori + self.n_pos
+        W = torch.empty((n, self.K), dtype=torch.float32, device=self.device)
+        b = torch.empty(n, dtype=torch.float32, device=self.device)
+        L.check(self.lib.spef_headfit_get_weights(self.handle, _ptr(W), _ptr(b), _stream(self.device)))
+        return W, b
+
+    def set_weights(self, W, b) -> None:
+        n = self.n_ori + self.n_pos
+        W = torch.as_tensor(W, dtype=torch.float32).to(self.device).contiguous()
+        b = torch.as_tensor(b, dtype=torch.float32).to(self.device).contiguous()
+        assert tuple(W.shape) == (n, self.K) and tuple(b.shape) == (n,)
+        L.check(self.lib.spef_headfit_set_weights(self.handle, _ptr(W), _ptr(b), _stream(self.device)))
+
+    def state(self):
+        """The optimizer state as device copies: SGD -> (buf_W, buf_b); Adam -> (m_W, m_b, v_W, v_b)."""
+        n = self.n_ori + self.n_pos
+        k = 4 if self.optimizer == 'adam' else 2
+        t = [torch.empty((n, self.K) if i % 2 == 0 else (n,), dtype=torch.float32, device=self.device)
+             for i in range(k)]
+        t += [None] * (4 - k)
+        L.check(self.lib.spef_headfit_get_state(self.handle, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), _ptr(t[3]),
+                                                _stream(self.device)))
+        return tuple(t[:k])
+
+    def last_g(self, B: int) -> torch.Tensor:
+        """G = dLoss/dlogits [B x (n_ori + n_pos)] of the last ``step`` / ``evaluate`` of B rows (inspection)."""
+        G = torch.empty((B, self.n_ori + self.n_pos), dtype=torch.float32, device=self.device)
+        L.check(self.lib.spef_headfit_get_g(self.handle, int(B), _ptr(G), _stream(self.device)))
+        return G
+
+    def raw(self, which: str) -> torch.Tensor:
+        """One of the trainer's tensors as it lies in memory, padding rows included (inspection): 'W', 'W_s1', 'W_s2'
+        [Np x K], 'bias', 'bias_s1', 'bias_s2' [Np] (Np = the widths rounded up to 16; the _s2 tensors under Adam only),
+        'Xd' [Bmax x K] (the dropout copy of X the last training step wrote; with dropout on only)."""
+        Np = (self.n_ori + self.n_pos + 15) // 16 * 16
+        shape = (self.Bmax, self.K) if which == 'Xd' else (Np, self.K) if which.startswith('W') else (Np,)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        L.check(self.lib.spef_headfit_get_raw(self.handle, L.HEADFIT_RAW[which], _ptr(out), _stream(self.device)))
+        return out
+
+    def reset_state(self) -> None:
+        """Zero the optimizer state and the step counter; enqueued."""
+        L.check(self.lib.spef_headfit_reset_state(self.handle, _stream(self.device)))
+
+    def load_model(self) -> None:
+        """Copy the engine's head into the trainer (the sizes must be the loaded blob's)."""
+        L.check(self.lib.spef_headfit_load_model(self.handle, self.engine.ctx, _stream(self.device)))
+
+    def commit(self) -> None:
+        """Copy the trainer's head into the engine: ``Engine.forward`` uses it from the next call on."""
+        L.check(self.lib.spef_headfit_commit(self.handle, self.engine.ctx, _stream(self.device)))
+        self.engine.epoch += 1
+
+    def close(self) -> None:
+        if getattr(self, 'handle', None):
+            torch.cuda.synchronize(self.device)
+            self.lib.spef_headfit_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """Loaded weights + workspace on one GPU.
 
@@ -532,7 +674,7 @@ class Engine:
         # bumped by every call that moves device buffers or changes what a recorded forward / decode would do
         # (workspace reallocation, weights, decode tables, options, camera): StreamPipeline's recorded HIP graphs key on it
         self.epoch = 0
-        self.head = self.n_out0 = self.n_out1 = self.n_ops = None
+        self.head = self.n_out0 = self.n_out1 = self.n_ops = self.feat_c = None
         self.dtype = None
         self.blob = None
         if blob is not None:
@@ -562,6 +704,9 @@ class Engine:
         self.head, self.n_out0, self.n_out1 = head.value, n0.value, n1.value
         self.dtype = {1: 'fp16', 2: 'bf16', 3: 'int8', 4: 'fp32', 5: 'fp16x2', 6: 'fp16mx'}[dt.value]
         self.n_ops = nops.value
+        fc = C.c_int()
+        L.check(self.lib.spef_feature_width(self.ctx, C.byref(fc)))
+        self.feat_c = fc.value   # the width of a `features` row
         self._reserved = (0, 0, 0)
         self.epoch += 1
 
@@ -677,6 +822,71 @@ class Engine:
         f = torch.empty((B, fh, fw, 1280), dtype=torch.float32, device=self.device)
         L.check(self.lib.spef_backbone(self.ctx, _ptr(x), layout, B, H, W, _ptr(f), _stream(self.device)))
         return f
+
+    def features(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The pooled backbone features fp32 [B x feat_c] (1280 for MobileNetV2) of frames ``x`` (either layout of
+        ``forward``): what ``forward`` hands to the head at the same schedule, bit for bit. URSONet float blobs only."""
+        assert x.device == self.device and x.is_contiguous()
+        layout, B, H, W = self._layout(x)
+        self.reserve(B, H, W)
+        if out is None:
+            out = torch.empty((B, self.feat_c), dtype=torch.float32, device=self.device)
+        assert out.device == self.device and out.dtype == torch.float32 and out.is_contiguous()
+        assert out.numel() == B * self.feat_c
+        L.check(self.lib.spef_features(self.ctx, _ptr(x), layout, B, H, W, _ptr(out), _stream(self.device)))
+        return out
+
+    def encode_targets(self, quat=None, pos=None, ori_var: Optional[float] = None, pos_var: Optional[float] = None,
+                       mask=None) -> dict:
+        """The reference's soft-classification targets (``OrientationSoftClassification.encode`` /
+        ``PositionSoftClassification.encode``) of B poses on this engine's decode tables, on the device. ``quat``
+        [B x 4] / ``pos`` [B x 3] (float64; either may be None), ``ori_var`` / ``pos_var`` = (smooth / n_bins_per_dim)^2
+        / 12 (defaults: the reference's smooth 3 over 12 bins and 100 over 10), ``mask`` = the redundant-bin flags
+        [n_ori]. -> {'ori_soft', 'pos_soft' (float32), 'status' int32 [B x 2]: 1 = that row of that head is NaN}."""
+        from .solver import head_fit as HF
+        assert quat is not None or pos is not None
+        dev = self.device
+
+        def f64(a, w):
+            if a is None:
+                return None
+            if not isinstance(a, torch.Tensor):
+                a = torch.from_numpy(np.ascontiguousarray(a, np.float64))
+            t = a.to(device=dev, dtype=torch.float64).contiguous()
+            assert t.dim() == 2 and t.shape[1] == w
+            return t
+        q, t = f64(quat, 4), f64(pos, 3)
+        B = (q if q is not None else t).shape[0]
+        assert t is None or q is None or t.shape[0] == q.shape[0]
+        ob, pg = self._decode_tables or (None, None)
+        assert (q is None or ob is not None) and (t is None or pg is not None), 'decode table not set'
+        out = {'status': torch.empty((B, 2), dtype=torch.int32, device=dev)}
+        if q is not None:
+            out['ori_soft'] = torch.empty((B, ob.shape[0]), dtype=torch.float32, device=dev)
+        if t is not None:
+            out['pos_soft'] = torch.empty((B, pg.shape[0]), dtype=torch.float32, device=dev)
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(np.ascontiguousarray(np.asarray(mask), np.uint8)).to(dev)
+            assert ob is not None and m.numel() == ob.shape[0]
+        prm = L.EncodeParams(HF.soft_variance(3, 12) if ori_var is None else float(ori_var),
+                             HF.soft_variance(100, 10) if pos_var is None else float(pos_var))
+        L.check(self.lib.spef_encode_targets(self.ctx, _ptr(q), _ptr(t), B, C.byref(prm), _ptr(m),
+                                             _ptr(out.get('ori_soft')), _ptr(out.get('pos_soft')), _ptr(out['status']),
+                                             _stream(dev)))
+        return out   # (q, t, m are stream-ordered temporaries of torch's allocator: the kernel reads them before any reuse)
+
+    def head_trainer(self, K: Optional[int] = None, n_ori: Optional[int] = None, n_pos: Optional[int] = None,
+                     **params) -> 'HeadTrainer':
+        """A head fit on this engine's device (``HeadTrainer``). Without sizes it takes the loaded URSONet blob's (its
+        feature width and its two head widths) and starts from the blob's head; with sizes it is a standalone trainer that starts
+        at zero weights."""
+        if K is None and n_ori is None and n_pos is None:
+            assert self.head == 0, 'no URSONet blob loaded: give K, n_ori, n_pos'
+            tr = HeadTrainer(self, self.feat_c, self.n_out0, self.n_out1, **params)
+            tr.load_model()
+            return tr
+        return HeadTrainer(self, K, n_ori, n_pos, **params)
 
     def probe(self, x: torch.Tensor, stop_op: int) -> torch.Tensor:
         layout, B, H, W = self._layout(x)
